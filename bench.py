@@ -1,6 +1,6 @@
 """bench.py -- MC trial-moves/s of the checkerboard Metropolis hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|5box]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|5box] [--full] [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...     (one rank per GPU, z-slab decomposition)
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py launches the N rank processes
@@ -25,11 +25,23 @@ in HBM; w=rc=2.5, beta=0.3, sigma=0.5, n_M=10, nmax=16, Philox seed 1234, refere
                           the halos travel through a one-rank RCCL communicator (rehearsal).
   5box                    the whole 256^3 / 8e7 box on one GPU.
 
-Rank 0 prints ONE JSON line: value = trial moves per second over all ranks; the roofline of the
-dominant kernel (subsweep: algorithmic bytes per launch / HIP-event launch time vs 8 TB/s); the
-CPU baseline (the C oracle: serial on one core and OpenMP over the cells of a colour on one
-socket's cores, bounded samples, host CPU described); and the parity leg (the CPU sample's sweep
-rerun on the GPU and compared with the oracle bit for bit).
+Rank 0 prints ONE JSON line: value = trial moves per second over all ranks, ms_per_step = the wall
+time of the --steps timed steps / --steps.  A plain run does only what that figure needs: set-up,
+warm-up, the timed steps (no per-launch events), the line.
+
+--full adds everything else, on the line as well: the roofline of the dominant kernel (subsweep:
+algorithmic bytes per launch / HIP-event launch time vs 8 TB/s, per-launch events in the timed
+region, the measured HBM rate); the energy bookkeeping of the timed steps; the CPU baseline (the C
+oracle: serial on one core and OpenMP over the cells of a colour on one socket's cores, bounded
+samples, host CPU described); and the parity leg (the CPU sample's sweep rerun on the GPU and
+compared with the oracle bit for bit).  --no-cpu-baseline, --no-events, --no-hbm-probe,
+--timing-every, --cpu-sweeps and --serial-planes trim or shape those legs and mean nothing without
+--full.
+
+--dump-outputs DIR writes what the last timed step left (the state a caller of the sweep path
+reads back with copy_out, and the counters) as DIR/<name>.npy: see dump_outputs.  Inputs are fixed
+(lattice start, Philox seed 1234), so two builds run with the same arguments can be compared array
+for array.
 """
 from __future__ import annotations
 
@@ -402,6 +414,44 @@ def rewarm(sim, one_sweep, finish, first: int, count: int, relink=None) -> None:
     sim.stats(reset=True)
     del save
 
+
+DUMP_SAMPLE_CELLS = 131072      # cells whose coordinates are dumped (all ranks together): 25 MB
+DUMP_ALL_COUNTS_CELLS = 4 << 20  # boxes up to this many cells dump every cell's count (16 MB)
+
+
+def dump_outputs(out_dir: str, sim, stats: dict, first_cell: int, owned_cells: int, rank: int, world: int) -> None:
+    """--dump-outputs: what the last timed step left, as float32/float64 .npy files (every rank its own,
+    `<name>_rank<r>` at N > 1; under 64 MB in all):
+      sample_cells  the sampled cells (indices into this rank's owned cells; a fixed seeded choice, all
+                    cells of a small box), float64
+      coords        their coordinates, (cells, 3, nmax) float32 in the reference row layout, the slots
+                    past a cell's count (never defined) zeroed
+      counts_sample their particle counts, float32
+      counts        every owned cell's count, float32 (boxes up to DUMP_ALL_COUNTS_CELLS cells)
+      stats         [trials, accepted, evaluated, sum of accepted dE] of the timed steps, float64"""
+    os.makedirs(out_dir, exist_ok=True)
+    disk, n = sim.copy_out()
+    nmax = sim.nmax
+    n = n[first_cell:first_cell + owned_cells]
+    disk = disk.reshape(-1, 3, nmax)[first_cell:first_cell + owned_cells]
+    k = max(1, DUMP_SAMPLE_CELLS // world)
+    if owned_cells <= k:
+        cells = np.arange(owned_cells)
+    else:
+        cells = np.sort(np.random.default_rng(1234).choice(owned_cells, size=k, replace=False))
+    cnt = n[cells].astype(np.int64)
+    coords = np.where(np.arange(nmax)[None, None, :] < cnt[:, None, None], disk[cells], np.float32(0.0))
+    sfx = f"_rank{rank}" if world > 1 else ""
+    arrays = {"sample_cells": cells.astype(np.float64), "coords": coords.astype(np.float32),
+              "counts_sample": cnt.astype(np.float32),
+              "stats": np.array([stats["trials"], stats["accepted"], stats["evaluated"],
+                                 stats["de_fixed"] / 2.0 ** 32], np.float64)}
+    if owned_cells * world <= DUMP_ALL_COUNTS_CELLS:
+        arrays["counts"] = n.astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+
+
 def _free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -479,6 +529,11 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=["2", "3", "4", "5", "5box"], default=None,
                     help="BASELINE config (default: 3 at N=1, 4 at N>1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: roofline (per-launch "
+                         "events, algorithmic bytes, HBM probe), energy bookkeeping, CPU baseline, parity leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state and counters after the last timed step as DIR/<name>.npy")
     ap.add_argument("--strong", action="store_true", help="alias of --config 4")
     ap.add_argument("--cps", type=int, default=None, help="override cells per side (configs 3/4)")
     ap.add_argument("--atoms", type=int, default=None, help="override the particle count (configs 3/4)")
@@ -645,66 +700,69 @@ def main() -> int:
     finish()
     torch.cuda.synchronize()
     sim.stats(reset=True)
-    # algorithmic bytes from the state at the start of the timed region
-    disk_h, n_h = sim.copy_out()
     plane = cps * cps
-    if config == "2":
-        # the timed steps' colours (no shiftCells: the counts, hence the bytes, stay fixed)
-        n_owned = n_h.astype(np.int64)
-        stencil = stencil_counts(n_owned, (cps, cps, cps))
-        idx = np.arange(cps ** 3)
-        cx, cy, cz = idx % cps, (idx // cps) % cps, idx // (cps * cps)
-        per_colour = []
-        for colour in range(8):
-            o = (colour // 4) % 2, (colour // 2) % 2, colour % 2     # itoa, start.cu:153-157
-            m = (cx % 2 == o[0]) & (cy % 2 == o[1]) & (cz % 2 == o[2])
-            per_colour.append(staged_bytes(n_owned[m], stencil[m]))
-        timed = [per_colour[(args.warmup + k) % 8] for k in range(args.steps)]
-        sub_launch_bytes = float(np.mean(timed))
-        roof_kernel = "k_subsweep<16,16,true> (one colour phase of the 64^3 box; mean over the timed steps' colours)"
-    elif not slab:
-        n_owned = n_h.astype(np.int64)
-        stencil = stencil_counts(n_owned, (cps, cps, cps))
-        phase_bytes = staged_bytes(n_owned, stencil) / 8.0
-        # pmc_sweep's plane chains (pmc_sweep_layout): each colour phase is one launch per chain, the
-        # chains' launches concurrent and a chain's next phase overlapping the others' tails; the
-        # roofline is per PHASE: a timed sweep's subsweep span (first launch start to last stop, HIP
-        # events on the dispatch packets; gaps included, shiftCells not) / 8, launch_ms the per-launch mean
-        sweep_chains = sim.sweep_layout()
-        per_chain = [staged_bytes(n_owned[a * plane:b * plane], stencil[a * plane:b * plane]) / 8.0
-                     for a, b in sweep_chains]
-        sub_launch_bytes = sum(per_chain) / len(per_chain)
-        roof_kernel = ("k_subsweep<16,16,true> (one colour phase of the whole box" +
-                       (f" as {len(sweep_chains)} concurrent launches, plane chains " +
-                        " and ".join(f"[{a},{b})" for a, b in sweep_chains) +
-                        "; achieved/frac per phase: a sweep's subsweep span / 8" if len(sweep_chains) > 1 else "") + ")")
-    else:
-        n_owned = n_h[plane * drv.halo:plane * (nz_local + drv.halo)].astype(np.int64)
-        stencil = slab_stencil_counts(n_h, cps, nz_local, drv.halo)
-        # kind-0 launches: the interior chains (pmc_slab_layout: 1-3 chains, PMC_SLAB_CHAINS), one
-        # launch per chain and colour phase; the roofline's bytes per launch are their mean (the
-        # chains run concurrently)
-        chains = [(a, b) for a, b in drv.ctx.slab_layout() if b > a]
-        per_chain = [staged_bytes(n_owned[a * plane:b * plane], stencil[a * plane:b * plane]) / 8.0
-                     for a, b in chains]
-        sub_launch_bytes = sum(per_chain) / len(per_chain) if per_chain else 0.0
-        roof_kernel = ("k_subsweep<16,16,true> (a slab colour phase's interior launches, planes "
-                       + " and ".join(f"[{a},{b})" for a, b in chains) + ", mean bytes per launch; "
-                       "per CHAIN: the chains run concurrently and share HBM, so achieved/frac describe "
-                       "one chain's launch, not the chip's rate)")
-    e_start = sim.energy()      # cell-list energy of the state the timed region starts from
-    # The host analysis above leaves the GPU idle, and an idle MI355X comes back at a lower clock:
+    if args.full:
+        # algorithmic bytes from the state at the start of the timed region
+        disk_h, n_h = sim.copy_out()
+        if config == "2":
+            # the timed steps' colours (no shiftCells: the counts, hence the bytes, stay fixed)
+            n_owned = n_h.astype(np.int64)
+            stencil = stencil_counts(n_owned, (cps, cps, cps))
+            idx = np.arange(cps ** 3)
+            cx, cy, cz = idx % cps, (idx // cps) % cps, idx // (cps * cps)
+            per_colour = []
+            for colour in range(8):
+                o = (colour // 4) % 2, (colour // 2) % 2, colour % 2     # itoa, start.cu:153-157
+                m = (cx % 2 == o[0]) & (cy % 2 == o[1]) & (cz % 2 == o[2])
+                per_colour.append(staged_bytes(n_owned[m], stencil[m]))
+            timed = [per_colour[(args.warmup + k) % 8] for k in range(args.steps)]
+            sub_launch_bytes = float(np.mean(timed))
+            roof_kernel = "k_subsweep<16,16,true> (one colour phase of the 64^3 box; mean over the timed steps' colours)"
+        elif not slab:
+            n_owned = n_h.astype(np.int64)
+            stencil = stencil_counts(n_owned, (cps, cps, cps))
+            phase_bytes = staged_bytes(n_owned, stencil) / 8.0
+            # pmc_sweep's plane chains (pmc_sweep_layout): each colour phase is one launch per chain, the
+            # chains' launches concurrent and a chain's next phase overlapping the others' tails; the
+            # roofline is per PHASE: a timed sweep's subsweep span (first launch start to last stop, HIP
+            # events on the dispatch packets; gaps included, shiftCells not) / 8, launch_ms the per-launch mean
+            sweep_chains = sim.sweep_layout()
+            per_chain = [staged_bytes(n_owned[a * plane:b * plane], stencil[a * plane:b * plane]) / 8.0
+                         for a, b in sweep_chains]
+            sub_launch_bytes = sum(per_chain) / len(per_chain)
+            roof_kernel = ("k_subsweep<16,16,true> (one colour phase of the whole box" +
+                           (f" as {len(sweep_chains)} concurrent launches, plane chains " +
+                            " and ".join(f"[{a},{b})" for a, b in sweep_chains) +
+                            "; achieved/frac per phase: a sweep's subsweep span / 8" if len(sweep_chains) > 1 else "") + ")")
+        else:
+            n_owned = n_h[plane * drv.halo:plane * (nz_local + drv.halo)].astype(np.int64)
+            stencil = slab_stencil_counts(n_h, cps, nz_local, drv.halo)
+            # kind-0 launches: the interior chains (pmc_slab_layout: 1-3 chains, PMC_SLAB_CHAINS), one
+            # launch per chain and colour phase; the roofline's bytes per launch are their mean (the
+            # chains run concurrently)
+            chains = [(a, b) for a, b in drv.ctx.slab_layout() if b > a]
+            per_chain = [staged_bytes(n_owned[a * plane:b * plane], stencil[a * plane:b * plane]) / 8.0
+                         for a, b in chains]
+            sub_launch_bytes = sum(per_chain) / len(per_chain) if per_chain else 0.0
+            roof_kernel = ("k_subsweep<16,16,true> (a slab colour phase's interior launches, planes "
+                           + " and ".join(f"[{a},{b})" for a, b in chains) + ", mean bytes per launch; "
+                           "per CHAIN: the chains run concurrently and share HBM, so achieved/frac describe "
+                           "one chain's launch, not the chip's rate)")
+        e_start = sim.energy()      # cell-list energy of the state the timed region starts from
+    # The host analysis above (--full) leaves the GPU idle, and an idle MI355X comes back at a lower clock:
     # after a 0.5 s gap the first sweeps take 3.0-3.3 ms and the rate settles at 2.53 ms only
     # after ~10 sweeps, even when the gap is filled with other GPU work (energy evaluations:
     # first sweep 2.71 ms, same ramp; profiles/r02s2_clock_ramp.txt).  So the hot path itself runs
     # `rewarm` sweeps on the timed start state right before the timed region, and the state is
     # then restored by device-to-device copies: the timed region starts from exactly the state
-    # analysed above, at the steady clock.  The counters of the re-warm sweeps are discarded.
+    # analysed above, at the steady clock.  The counters of the re-warm sweeps are discarded.  A
+    # plain run re-warms too: its few warm-up sweeps alone do not reach the steady clock either.
     if args.rewarm > 0:
         rewarm(sim, one_sweep, finish, first=args.warmup, count=args.rewarm,
                relink=(lambda: drv.ctx.slab_exchange()) if slab else None)
 
-    sim.timing_kinds(not args.no_events and not args.graph)
+    events = args.full and not args.no_events       # per-launch HIP events: the roofline's kernel times
+    sim.timing_kinds(events and not args.graph)
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -713,7 +771,7 @@ def main() -> int:
     if args.graph and not slab:
         sim.run_graph(first, args.steps)
     else:
-        timed = not args.no_events
+        timed = events
         every = args.timing_every if args.timing_every > 0 else (max(4, -(-args.steps // 2)) if slab else 4)
         for k in range(args.steps):
             if timed and every > 1:
@@ -739,144 +797,149 @@ def main() -> int:
         trials_total, accepted_total = trials_local, st["accepted"]
     flags = sim.error_flags()
     value = trials_total / elapsed
-    # energy bookkeeping over the timed sweeps: E_start + sum of accepted dE (fixed point 2^-32,
-    # order-independent) against a direct cell-list evaluation of the final state
-    e_end = sim.energy()
-    de_timed = st["de_fixed"] / 2.0 ** 32
-    if world > 1:   # slab energies count boundary pairs half on each side: the sum is the box's
-        ev = torch.tensor([e_start, e_end, de_timed], dtype=torch.float64)
-        dist.all_reduce(ev)
-        e_start, e_end, de_timed = (float(v) for v in ev.tolist())
-    particles = int(n_owned.sum())
-    if world > 1:
-        pt = torch.tensor([particles], dtype=torch.int64)
-        dist.all_reduce(pt)
-        particles = int(pt.item())
-    # node roofline (north_star: "fraction of the HBM roofline at 1, 2, 4 and 8 GPUs"): the staged
-    # model's bytes of one step summed over the ranks -- every owned cell's visit plus
-    # shiftCells' 36 B per particle + 6 B per cell -- over the step time, against N x 8 TB/s
-    if config == "2":
-        step_bytes_local = sub_launch_bytes
-        step_shift_local = 0.0
-    else:
-        step_bytes_local = staged_bytes(n_owned, stencil)
-        step_shift_local = float(36 * int(n_owned.sum()) + 6 * n_owned.size)
-    sb = torch.tensor([step_bytes_local, step_shift_local], dtype=torch.float64)
-    if world > 1:
-        dist.all_reduce(sb)
-    step_bytes, step_shift_bytes = (float(v) for v in sb.tolist())
-    # the rate this box actually delivers, measured on rank 0's GPU
-    hbm_meas = achievable_hbm() if (rank == 0 and not args.no_hbm_probe) else None
-
-    if rank == 0:
-        n_launch = tm["n_subsweep"]
-        avg_launch_s = (tm["subsweep_ms"] / n_launch * 1e-3) if n_launch else None
-        achieved = (sub_launch_bytes / avg_launch_s / 1e9) if avg_launch_s else None
-        phase_s = (span_ms / span_n * 1e-3) if span_n else None
-        if phase_s:   # chained whole-box phases: bytes of a phase over the phase's span
-            achieved = phase_bytes / phase_s / 1e9
-        traffic = traffic_from_profile(config, slab, nz_local)
-        # FP32 work of the moves (14 FLOP per pair evaluation, old + new position,
-        # against the S_c - 1 stencil partners of each evaluated move; the mean stencil of the
-        # visited cells stands for each cell's) per launch, over the HIP-event launch time
-        fp32 = None
-        if avg_launch_s and not slab:
-            ne = n_owned > 0
-            s_mean = float(stencil[ne].mean()) if ne.any() else 0.0
-            phases = args.steps * (1 if config == "2" else 8)
-            flop = 28.0 * st["evaluated"] / phases * max(s_mean - 1.0, 0.0)     # per colour phase
-            t_ph = phase_s or avg_launch_s
-            fp32 = {"achieved": flop / t_ph / 1e12, "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": flop / t_ph / 1e12 / FP32_PEAK_TFLOPS, "flop_per_phase": flop,
-                    "model": "28 FLOP x (mean stencil - 1) per evaluated move (SURVEY.md 8d), per colour phase"}
-        valu = valu_from_profile() if config == "3" else None   # profiled on the config-3 launch
-        shift_bytes = None
-        if tm["n_shift"]:
-            # shiftCells (VS shiftCells.h:23-112): per output cell, read its own occupied slots and
-            # those of its dir-neighbour with both counts, write the new occupied slots and count --
-            # 12 B per particle read twice (own and as a neighbour) and written once, 6 B of counts
-            shift_bytes = float(36 * int(n_owned.sum()) + 6 * n_owned.size)
-        roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                "traffic": traffic.get("subsweep_bytes_per_launch") if traffic else None,
-                "traffic_source": traffic.get("source") if traffic else None,
-                "kernel": roof_kernel,
-                "launch_ms": avg_launch_s * 1e3 if avg_launch_s else None,
-                "launches_timed": n_launch,
-                **({"phase_ms": phase_s * 1e3, "phases_timed": span_n,
-                    "algorithmic_bytes_per_phase": phase_bytes,
-                    # the per-launch view rocprofv3's kernel statistics give (half-box launches, two at once)
-                    "launch_achieved": sub_launch_bytes / avg_launch_s / 1e9 if avg_launch_s else None}
-                   if phase_s else {}),
-                "shift_ms": tm["shift_ms"] / tm["n_shift"] if tm["n_shift"] else None,
-                "shift": ({"algorithmic_bytes_per_launch": shift_bytes,
-                           "achieved": shift_bytes / (tm["shift_ms"] / tm["n_shift"] * 1e-3) / 1e9,
-                           "frac": shift_bytes / (tm["shift_ms"] / tm["n_shift"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                           "model": "36 B per particle + 6 B per cell (own + neighbour occupied slots read, "
-                                    "new slots written, counts)"}
-                          if shift_bytes and tm["n_shift"] and tm["shift_ms"] > 0 else None),
-                "fp32": fp32,
-                "valu": valu,
-                "binding": ("valu-issue (roofline.valu.frac; HBM frac and fp32 frac are far below it)"
-                            if valu else None),
-                "boundary_launch_ms": tm["boundary_ms"] / tm["n_boundary"] if tm["n_boundary"] else None,
-                "algorithmic_bytes_per_launch": sub_launch_bytes}
-        ms_step = elapsed / args.steps
-        node_ach = (step_bytes + step_shift_bytes) / ms_step / 1e9
-        roof["node"] = {
-            "achieved": node_ach, "peak": HBM_PEAK_GBS * world, "unit": "GB/s",
-            "frac": node_ach / (HBM_PEAK_GBS * world),
-            "bytes_per_step": step_bytes + step_shift_bytes, "subsweep_bytes_per_step": step_bytes,
-            "shift_bytes_per_step": step_shift_bytes, "gpus": world,
-            "model": ("sum over ranks of the staged model's bytes of one step (every owned non-empty cell: "
-                      "12 B x stencil particles + 54 B of counts + 12 B x own particles written; shiftCells "
-                      "36 B per particle + 6 B per cell) / ms_per_step, against N x 8 TB/s")}
-        if hbm_meas:
-            roof["achievable_peak"] = hbm_meas
-            # the subsweep reads ~25x what it writes: its achievable roof is the read rate
-            roof["frac_of_achievable"] = (achieved / hbm_meas["read_GBs"]) if achieved else None
-            roof["node"]["frac_of_achievable"] = node_ach / (hbm_meas["read_GBs"] * world)
-    # CPU baseline and parity leg (after the timed region).  Slabs: the start state of the timed
-    # region is gathered on rank 0 (the whole box), the oracle runs there while the other ranks wait,
-    # then every rank reruns the sample's sweep (collective) and rank 0 compares.
-    cpu = None
-    parity = None
-    if not args.no_cpu_baseline:
-        sp = args.serial_planes or min(cps, 128)
-        ost = None
-        if not slab:
-            if rank == 0:
-                try:
-                    ph = (first % 8, first // 8) if config == "2" else None
-                    cs = 1 if ph else max(1, args.cpu_sweeps)
-                    cpu, ost = cpu_baseline(disk_h, n_h, cps, first, sp, phase=ph, sweeps=cs)
-                    parity = parity_leg(sim, one_sweep, disk_h, n_h, first, cs, e_start, ost)
-                    if config == "2":
-                        parity["sweeps"] = 0
-                        parity["phase"] = {"colour": first % 8, "sweep_index": first // 8}
-                except Exception as e:  # the baseline is reported, never the measured value
-                    cpu = {"error": repr(e)}
+    if args.dump_outputs:   # before the --full legs: the parity leg reruns sweeps from another state
+        h = drv.halo if slab else 0
+        dump_outputs(args.dump_outputs, sim, st, first_cell=h * plane, owned_cells=nz_local * plane,
+                     rank=rank, world=world)
+    if args.full:
+        # energy bookkeeping over the timed sweeps: E_start + sum of accepted dE (fixed point 2^-32,
+        # order-independent) against a direct cell-list evaluation of the final state
+        e_end = sim.energy()
+        de_timed = st["de_fixed"] / 2.0 ** 32
+        if world > 1:   # slab energies count boundary pairs half on each side: the sum is the box's
+            ev = torch.tensor([e_start, e_end, de_timed], dtype=torch.float64)
+            dist.all_reduce(ev)
+            e_start, e_end, de_timed = (float(v) for v in ev.tolist())
+        particles = int(n_owned.sum())
+        if world > 1:
+            pt = torch.tensor([particles], dtype=torch.int64)
+            dist.all_reduce(pt)
+            particles = int(pt.item())
+        # node roofline (north_star: "fraction of the HBM roofline at 1, 2, 4 and 8 GPUs"): the staged
+        # model's bytes of one step summed over the ranks -- every owned cell's visit plus
+        # shiftCells' 36 B per particle + 6 B per cell -- over the step time, against N x 8 TB/s
+        if config == "2":
+            step_bytes_local = sub_launch_bytes
+            step_shift_local = 0.0
         else:
-            gather = make_gather(world, rank, plane, nz_local, 3 * 16, drv.halo)
-            whole = gather(disk_h, n_h)
-            # the sample: --cpu-sweeps sweeps from the timed start state, at the first sweep indices that
-            # shift along z both ways (every exchange kind, the deferred z planes included, on the node)
-            cs = max(1, args.cpu_sweeps)
-            s0 = z_shift_window(sim.params.seed, first, cs)
-            if rank == 0:
-                try:
-                    cpu, ost = cpu_baseline(whole[0], whole[1], cps, s0, sp, cps_z=box_z, sweeps=cs)
-                    cpu["sample"] += f" (whole {cps}x{cps}x{box_z} box gathered from {world} rank(s))"
-                except Exception as e:
-                    cpu = {"error": repr(e)}
-            del whole
-            barrier()
-            ok = torch.tensor([1 if (rank != 0 or ost is not None) else 0])
-            if world > 1:
-                dist.broadcast(ok, src=0)
-            if int(ok.item()):
-                parity = parity_leg_slab(sim, one_sweep, finish, disk_h, n_h, s0, e_start, gather, ost, rank,
-                                         sweeps=cs)
+            step_bytes_local = staged_bytes(n_owned, stencil)
+            step_shift_local = float(36 * int(n_owned.sum()) + 6 * n_owned.size)
+        sb = torch.tensor([step_bytes_local, step_shift_local], dtype=torch.float64)
+        if world > 1:
+            dist.all_reduce(sb)
+        step_bytes, step_shift_bytes = (float(v) for v in sb.tolist())
+        # the rate the HBM actually delivers, measured on rank 0's GPU
+        hbm_meas = achievable_hbm() if (rank == 0 and not args.no_hbm_probe) else None
+
+        if rank == 0:
+            n_launch = tm["n_subsweep"]
+            avg_launch_s = (tm["subsweep_ms"] / n_launch * 1e-3) if n_launch else None
+            achieved = (sub_launch_bytes / avg_launch_s / 1e9) if avg_launch_s else None
+            phase_s = (span_ms / span_n * 1e-3) if span_n else None
+            if phase_s:   # chained whole-box phases: bytes of a phase over the phase's span
+                achieved = phase_bytes / phase_s / 1e9
+            traffic = traffic_from_profile(config, slab, nz_local)
+            # FP32 work of the moves (14 FLOP per pair evaluation, old + new position,
+            # against the S_c - 1 stencil partners of each evaluated move; the mean stencil of the
+            # visited cells stands for each cell's) per launch, over the HIP-event launch time
+            fp32 = None
+            if avg_launch_s and not slab:
+                ne = n_owned > 0
+                s_mean = float(stencil[ne].mean()) if ne.any() else 0.0
+                phases = args.steps * (1 if config == "2" else 8)
+                flop = 28.0 * st["evaluated"] / phases * max(s_mean - 1.0, 0.0)     # per colour phase
+                t_ph = phase_s or avg_launch_s
+                fp32 = {"achieved": flop / t_ph / 1e12, "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": flop / t_ph / 1e12 / FP32_PEAK_TFLOPS, "flop_per_phase": flop,
+                        "model": "28 FLOP x (mean stencil - 1) per evaluated move (SURVEY.md 8d), per colour phase"}
+            valu = valu_from_profile() if config == "3" else None   # profiled on the config-3 launch
+            shift_bytes = None
+            if tm["n_shift"]:
+                # shiftCells (VS shiftCells.h:23-112): per output cell, read its own occupied slots and
+                # those of its dir-neighbour with both counts, write the new occupied slots and count --
+                # 12 B per particle read twice (own and as a neighbour) and written once, 6 B of counts
+                shift_bytes = float(36 * int(n_owned.sum()) + 6 * n_owned.size)
+            roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                    "traffic": traffic.get("subsweep_bytes_per_launch") if traffic else None,
+                    "traffic_source": traffic.get("source") if traffic else None,
+                    "kernel": roof_kernel,
+                    "launch_ms": avg_launch_s * 1e3 if avg_launch_s else None,
+                    "launches_timed": n_launch,
+                    **({"phase_ms": phase_s * 1e3, "phases_timed": span_n,
+                        "algorithmic_bytes_per_phase": phase_bytes,
+                        # the per-launch view rocprofv3's kernel statistics give (half-box launches, two at once)
+                        "launch_achieved": sub_launch_bytes / avg_launch_s / 1e9 if avg_launch_s else None}
+                       if phase_s else {}),
+                    "shift_ms": tm["shift_ms"] / tm["n_shift"] if tm["n_shift"] else None,
+                    "shift": ({"algorithmic_bytes_per_launch": shift_bytes,
+                               "achieved": shift_bytes / (tm["shift_ms"] / tm["n_shift"] * 1e-3) / 1e9,
+                               "frac": shift_bytes / (tm["shift_ms"] / tm["n_shift"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               "model": "36 B per particle + 6 B per cell (own + neighbour occupied slots read, "
+                                        "new slots written, counts)"}
+                              if shift_bytes and tm["n_shift"] and tm["shift_ms"] > 0 else None),
+                    "fp32": fp32,
+                    "valu": valu,
+                    "binding": ("valu-issue (roofline.valu.frac; HBM frac and fp32 frac are far below it)"
+                                if valu else None),
+                    "boundary_launch_ms": tm["boundary_ms"] / tm["n_boundary"] if tm["n_boundary"] else None,
+                    "algorithmic_bytes_per_launch": sub_launch_bytes}
+            ms_step = elapsed / args.steps
+            node_ach = (step_bytes + step_shift_bytes) / ms_step / 1e9
+            roof["node"] = {
+                "achieved": node_ach, "peak": HBM_PEAK_GBS * world, "unit": "GB/s",
+                "frac": node_ach / (HBM_PEAK_GBS * world),
+                "bytes_per_step": step_bytes + step_shift_bytes, "subsweep_bytes_per_step": step_bytes,
+                "shift_bytes_per_step": step_shift_bytes, "gpus": world,
+                "model": ("sum over ranks of the staged model's bytes of one step (every owned non-empty cell: "
+                          "12 B x stencil particles + 54 B of counts + 12 B x own particles written; shiftCells "
+                          "36 B per particle + 6 B per cell) / ms_per_step, against N x 8 TB/s")}
+            if hbm_meas:
+                roof["achievable_peak"] = hbm_meas
+                # the subsweep reads ~25x what it writes: its achievable roof is the read rate
+                roof["frac_of_achievable"] = (achieved / hbm_meas["read_GBs"]) if achieved else None
+                roof["node"]["frac_of_achievable"] = node_ach / (hbm_meas["read_GBs"] * world)
+        # CPU baseline and parity leg (after the timed region).  Slabs: the start state of the timed
+        # region is gathered on rank 0 (the whole box), the oracle runs there while the other ranks wait,
+        # then every rank reruns the sample's sweep (collective) and rank 0 compares.
+        cpu = None
+        parity = None
+        if not args.no_cpu_baseline:
+            sp = args.serial_planes or min(cps, 128)
+            ost = None
+            if not slab:
+                if rank == 0:
+                    try:
+                        ph = (first % 8, first // 8) if config == "2" else None
+                        cs = 1 if ph else max(1, args.cpu_sweeps)
+                        cpu, ost = cpu_baseline(disk_h, n_h, cps, first, sp, phase=ph, sweeps=cs)
+                        parity = parity_leg(sim, one_sweep, disk_h, n_h, first, cs, e_start, ost)
+                        if config == "2":
+                            parity["sweeps"] = 0
+                            parity["phase"] = {"colour": first % 8, "sweep_index": first // 8}
+                    except Exception as e:  # the baseline is reported, never the measured value
+                        cpu = {"error": repr(e)}
+            else:
+                gather = make_gather(world, rank, plane, nz_local, 3 * 16, drv.halo)
+                whole = gather(disk_h, n_h)
+                # the sample: --cpu-sweeps sweeps from the timed start state, at the first sweep indices that
+                # shift along z both ways (every exchange kind, the deferred z planes included, on the node)
+                cs = max(1, args.cpu_sweeps)
+                s0 = z_shift_window(sim.params.seed, first, cs)
+                if rank == 0:
+                    try:
+                        cpu, ost = cpu_baseline(whole[0], whole[1], cps, s0, sp, cps_z=box_z, sweeps=cs)
+                        cpu["sample"] += f" (whole {cps}x{cps}x{box_z} box gathered from {world} rank(s))"
+                    except Exception as e:
+                        cpu = {"error": repr(e)}
+                del whole
+                barrier()
+                ok = torch.tensor([1 if (rank != 0 or ost is not None) else 0])
+                if world > 1:
+                    dist.broadcast(ok, src=0)
+                if int(ok.item()):
+                    parity = parity_leg_slab(sim, one_sweep, finish, disk_h, n_h, s0, e_start, gather, ost, rank,
+                                             sweeps=cs)
 
     if rank == 0:
         sweeps_per_s = args.steps / elapsed / (8.0 if config == "2" else 1.0)
@@ -901,28 +964,35 @@ def main() -> int:
             "higher_is_better": True,
             # configs 3 -> 4 are one fixed box over 1..N GPUs (strong); config 5 fixes the work per GPU
             "scaling": "weak" if config == "5" else "strong",
-            # the same run's CPU baseline (one socket of the host, C oracle): BASELINE.json publishes
-            # no number, so the socket estimate is the denominator
-            "vs_baseline": (value / cpu["socket_estimate"]) if (cpu and cpu.get("socket_estimate")) else None,
-            "vs_baseline_of": "cpu_baseline.socket_estimate" if (cpu and cpu.get("socket_estimate")) else None,
             "dtype": "f32",
+            "full": args.full,
             "data": "synthetic (reference simple-cubic lattice start, Philox seed 1234)",
             "config": {"workload": name, "baseline_config": config,
                        "box_cells": [cps, cps, box_z], "cells_per_gpu": cps * cps * nz_local,
-                       "particles": particles, "n_moves": 10, "nmax": 16, "beta": 0.3, "sigma": 0.5,
+                       "n_moves": 10, "nmax": 16, "beta": 0.3, "sigma": 0.5,
                        "w": 2.5, "parallelism": transport,
                        **({"injected_exchange_delay_us": args.xfer_delay_us} if args.xfer_delay_us > 0 else {})},
             "sweeps_per_s": sweeps_per_s,
             "acceptance": accepted_total / trials_total if trials_total else None,
-            "energy": {"start": e_start, "end": e_end, "start_plus_sum_dE": e_start + de_timed,
-                       "per_particle_end": e_end / particles if particles else None,
-                       "bookkeeping_rel_err": abs(e_start + de_timed - e_end) / abs(e_end) if e_end else None,
-                       "particles": particles},
-            "parity": parity,
             "error_flags": flags,
-            "roofline": roof,
-            "cpu_baseline": cpu,
         }
+        if args.dump_outputs:
+            out["dump_outputs"] = args.dump_outputs
+        if args.full:
+            out["config"]["particles"] = particles
+            out.update({
+                # the same run's CPU baseline (one socket of the host, C oracle): BASELINE.json publishes
+                # no number, so the socket estimate is the denominator
+                "vs_baseline": (value / cpu["socket_estimate"]) if (cpu and cpu.get("socket_estimate")) else None,
+                "vs_baseline_of": "cpu_baseline.socket_estimate" if (cpu and cpu.get("socket_estimate")) else None,
+                "energy": {"start": e_start, "end": e_end, "start_plus_sum_dE": e_start + de_timed,
+                           "per_particle_end": e_end / particles if particles else None,
+                           "bookkeeping_rel_err": abs(e_start + de_timed - e_end) / abs(e_end) if e_end else None,
+                           "particles": particles},
+                "parity": parity,
+                "roofline": roof,
+                "cpu_baseline": cpu,
+            })
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

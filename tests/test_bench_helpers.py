@@ -85,6 +85,55 @@ def test_traffic_profile_is_per_launch_json():
     assert t["read_bytes_per_launch"] + t["write_bytes_per_launch"] > 0
 
 
+class _FakeSim:
+    """copy_out of a 2-halo-plane storage of `cells` cells with garbage (NaN) past each cell's count."""
+    nmax = 4
+
+    def __init__(self, cells, seed):
+        rng = np.random.default_rng(seed)
+        self.n = rng.integers(0, self.nmax + 1, size=cells).astype(np.int16)
+        self.disk = rng.random((cells, 3, self.nmax), dtype=np.float32) + 1.0
+        self.disk[np.arange(self.nmax)[None, None, :] >= self.n[:, None, None] + np.zeros((1, 3, 1), int)] = np.nan
+
+    def copy_out(self):
+        return self.disk.reshape(-1).copy(), self.n.copy()
+
+
+def test_dump_outputs_small_box_is_whole_and_masked(tmp_path):
+    """--dump-outputs: a box smaller than the sample is dumped whole, the owned cells only, float32 /
+    float64, undefined slots zeroed, the counters beside it."""
+    plane, nz = 9, 3
+    sim = _FakeSim((nz + 2) * plane, 7)
+    st = {"trials": 1000, "accepted": 400, "evaluated": 900, "de_fixed": -3 << 32}
+    bench.dump_outputs(str(tmp_path), sim, st, first_cell=plane, owned_cells=nz * plane, rank=0, world=1)
+    got = {f[:-4]: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert sorted(got) == ["coords", "counts", "counts_sample", "sample_cells", "stats"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    own = slice(plane, (nz + 1) * plane)
+    assert np.array_equal(got["sample_cells"], np.arange(nz * plane))
+    assert np.array_equal(got["counts"], sim.n[own]) and np.array_equal(got["counts_sample"], sim.n[own])
+    assert np.array_equal(got["coords"], np.nan_to_num(sim.disk[own], nan=0.0))
+    assert got["stats"].tolist() == [1000.0, 400.0, 900.0, -3.0]
+
+
+def test_dump_outputs_large_box_fixed_sample(tmp_path, monkeypatch):
+    """A box larger than the sample: the same seeded cells on every call (two builds compare array for
+    array), per-rank file names and a per-rank share of the sample at N > 1, no whole-box counts
+    beyond the size limit."""
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_CELLS", 64)
+    monkeypatch.setattr(bench, "DUMP_ALL_COUNTS_CELLS", 100)
+    sim = _FakeSim(500, 11)
+    st = {"trials": 1, "accepted": 1, "evaluated": 1, "de_fixed": 0}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), sim, st, first_cell=0, owned_cells=500, rank=1, world=2)
+    assert sorted(os.listdir(tmp_path / "a")) == [f"{k}_rank1.npy" for k in
+                                                  ("coords", "counts_sample", "sample_cells", "stats")]
+    a, b = (np.load(tmp_path / d / "sample_cells_rank1.npy").astype(int) for d in ("a", "b"))
+    assert np.array_equal(a, b) and a.size == 32 and np.all(np.diff(a) > 0) and a.max() < 500
+    assert np.array_equal(np.load(tmp_path / "a" / "counts_sample_rank1.npy"), sim.n[a])
+    assert np.array_equal(np.load(tmp_path / "a" / "coords_rank1.npy"), np.nan_to_num(sim.disk[a], nan=0.0))
+
+
 def _gather_rank(rank, world, port, cps, nz, q):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))

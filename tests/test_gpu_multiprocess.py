@@ -113,12 +113,12 @@ def test_ipc_processes_equal_oracle(pmc, oracle, tmp_path, world, cps, cps_z, at
 @pytest.mark.parametrize("world", [2, 8])
 def test_bench_rank_processes_same_device(pmc, world):
     """bench.py --gpus N launches N rank processes itself; with --same-device all use GPU 0 and the
-    halos go through the IPC transport (world 8: 4 planes per rank of the 32^3 box).  The N > 1 line
-    carries the gathered whole-box parity leg."""
+    halos go through the IPC transport (world 8: 4 planes per rank of the 32^3 box).  With --full the
+    N > 1 line carries the gathered whole-box parity leg, the CPU baseline and the roofline."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["PMC_IPC_TIMEOUT_S"] = "30"
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(world), "--same-device", "--config", "4",
-                        "--cps", "32", "--atoms", "120000", "--steps", "4", "--warmup", "2", "--rewarm", "2",
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", str(world), "--same-device",
+                        "--config", "4", "--cps", "32", "--atoms", "120000", "--steps", "4", "--warmup", "2", "--rewarm", "2",
                         "--serial-planes", "4", "--rank-timeout", "240"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -7,7 +7,7 @@ OUT=gpurun_out/sq_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU -T --output-format csv -d $OUT -o run -- \
-    python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/run.log 2>&1 || exit $?
+    python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/run.log 2>&1 || exit $?
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections
 agg = collections.defaultdict(list)

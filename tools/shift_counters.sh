@@ -6,7 +6,7 @@ set -o pipefail
 O=gpurun_out/shcnt_$1; mkdir -p $O
 export TMPDIR=/tmp
 run() { local n=$1; shift
-  timeout -s KILL 150 rocprofv3 --pmc "$@" --output-format csv -d $O/$n -o run -- python3 bench.py --steps 4 --warmup 2 --rewarm 0 --no-cpu-baseline > $O/$n.log 2>&1 || { tail -5 $O/$n.log; exit 1; }
+  timeout -s KILL 150 rocprofv3 --pmc "$@" --output-format csv -d $O/$n -o run -- python3 bench.py --full --steps 4 --warmup 2 --rewarm 0 --no-cpu-baseline > $O/$n.log 2>&1 || { tail -5 $O/$n.log; exit 1; }
 }
 run p1 FETCH_SIZE || exit 1
 run p2 WRITE_SIZE || exit 1

@@ -6,7 +6,7 @@ set -o pipefail
 O=gpurun_out/shtcc_$1; mkdir -p $O
 export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -s KILL 150 rocprofv3 --pmc $c --output-format csv -d $O/$c -o run -- python3 bench.py --steps 4 --warmup 2 --rewarm 0 --no-cpu-baseline > $O/$c.log 2>&1 || { tail -5 $O/$c.log; exit 1; }
+  timeout -s KILL 150 rocprofv3 --pmc $c --output-format csv -d $O/$c -o run -- python3 bench.py --full --steps 4 --warmup 2 --rewarm 0 --no-cpu-baseline > $O/$c.log 2>&1 || { tail -5 $O/$c.log; exit 1; }
 done
 python3 - $O <<'PY'
 import csv, glob, sys, collections, json

@@ -7,7 +7,7 @@
 set -o pipefail
 O=gpurun_out/slabtcc_$1; mkdir -p $O
 export TMPDIR=/tmp
-B="bench.py --steps 4 --warmup 2 --rewarm 0 --no-cpu-baseline"
+B="bench.py --full --steps 4 --warmup 2 --rewarm 0 --no-cpu-baseline"
 for shape in "4:16:--config 4 --emulate-ranks 8" "4:32:--config 4 --emulate-ranks 4" "4:64:--config 4 --emulate-ranks 2" "5:32:--config 5"; do
   key=${shape%%:--*}; args=--${shape#*:--}; d=$O/${key/:/_}
   for c in FETCH_SIZE WRITE_SIZE; do

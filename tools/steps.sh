@@ -64,29 +64,29 @@ for spec in "$@"; do
         mp) timeout -k 10 600 $PYT tests/test_gpu_multiprocess.py -m gpu > $log 2>&1 ;;
         file:*) timeout -k 10 700 $PYT ${step#file:} -m gpu > $log 2>&1 ;;
         smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $log 2>&1 ;;
-        bench) timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $log 2>&1 ;;
-        bench2) timeout -k 10 300 python bench.py --config 2 --steps 160 --warmup 8 > $log 2>&1 ;;
-        slab1) timeout -k 10 300 python bench.py --slab --no-cpu-baseline --steps 20 --warmup 5 > $log 2>&1 ;;
-        bench5) timeout -k 10 300 python bench.py --config 5 --no-cpu-baseline --steps 20 --warmup 5 > $log 2>&1 ;;
-        bench5box) timeout -k 10 400 python bench.py --config 5box --no-cpu-baseline --steps 10 --warmup 3 > $log 2>&1 ;;
+        bench) timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $log 2>&1 ;;
+        bench2) timeout -k 10 300 python bench.py --full --config 2 --steps 160 --warmup 8 > $log 2>&1 ;;
+        slab1) timeout -k 10 300 python bench.py --full --slab --no-cpu-baseline --steps 20 --warmup 5 > $log 2>&1 ;;
+        bench5) timeout -k 10 300 python bench.py --full --config 5 --no-cpu-baseline --steps 20 --warmup 5 > $log 2>&1 ;;
+        bench5box) timeout -k 10 400 python bench.py --full --config 5box --no-cpu-baseline --steps 10 --warmup 3 > $log 2>&1 ;;
         emu*)
             spec=${step#emu}; R=${spec%%-*}; tp=local; dl=0; extra=
             IFS=- read -ra parts <<< "$spec"
             for p in "${parts[@]:1}"; do
                 case $p in d*) dl=${p#d} ;; ne) extra=--no-events ;; t*) extra="--timing-every ${p#t}" ;; *) tp=$p ;; esac
             done
-            timeout -k 10 300 python bench.py --config 4 --emulate-ranks $R --transport $tp --xfer-delay-us $dl \
+            timeout -k 10 300 python bench.py --full --config 4 --emulate-ranks $R --transport $tp --xfer-delay-us $dl \
                 --no-cpu-baseline --steps 100 --warmup 20 $extra > $log 2>&1 ;;
-        mp2bench) timeout -k 10 400 python bench.py --gpus 2 --same-device --config 4 --steps 20 --warmup 5 \
+        mp2bench) timeout -k 10 400 python bench.py --full --gpus 2 --same-device --config 4 --steps 20 --warmup 5 \
                 --rank-timeout 360 > $log 2>&1 ;;
-        mp4bench|mp8bench) R=${step:2:1}; timeout -k 10 500 python bench.py --gpus $R --same-device --config 4 --steps 10 \
+        mp4bench|mp8bench) R=${step:2:1}; timeout -k 10 500 python bench.py --full --gpus $R --same-device --config 4 --steps 10 \
                 --warmup 3 --rank-timeout 460 > $log 2>&1 ;;
         rocprof) export TMPDIR=/tmp; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv \
-                -d $OUT/rocprof -o bench -- python3 bench.py --steps 20 --warmup 5 > $log 2>&1 ;;
+                -d $OUT/rocprof -o bench -- python3 bench.py --full --steps 20 --warmup 5 > $log 2>&1 ;;
         py:*) timeout -k 10 300 python tools/${step#py:} > $log 2>&1 ;;
         trace8*) dl=${step#trace8}; dl=${dl#d}; dl=${dl:-0}; export TMPDIR=/tmp
             timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/$name -o run \
-                -- python3 bench.py --config 4 --emulate-ranks 8 --transport ipc --xfer-delay-us $dl --no-cpu-baseline \
+                -- python3 bench.py --full --config 4 --emulate-ranks 8 --transport ipc --xfer-delay-us $dl --no-cpu-baseline \
                 --steps 40 --warmup 10 > $log 2>&1 \
                 && python3 tools/timeline_stats.py $OUT/$name/run_kernel_trace.csv 20 > $OUT/${name}_timeline.txt 2>&1 ;;
         tcc) timeout -k 10 600 bash tools/tcc_traffic.sh ${TAG}_$name > $log 2>&1 ;;
