@@ -2831,25 +2831,105 @@ int subsweep_capacity(const DevGeom& g) {
     return kMainCap < full ? kMainCap : full;
 }
 
+// dynamic LDS of a subsweep workgroup whose waves hold `cap` partners each
+static size_t lds_bytes(int cap) { return sizeof(float) * (size_t)lds_floats_per_wave(cap) * kSubWaves; }
+
+// cells of a colour phase over ncz colour planes
+static int64_t phase_cells(const DevGeom& g, int ncz) { return (int64_t)(g.cps_x / 2) * (g.cps_y / 2) * ncz; }
+
+// 32-bit byte offsets when the disk buffer (halo planes included) is below 4 GiB (every single-GPU
+// 256^3 config), else 64-bit addressing.  The env hooks on top of it are NOT symmetric: only
+// launch_subsweep reads PMC_FORCE_ADDR64, only the shift reads PMC_SHIFT_OFF32.
+static bool disk_off32(const DevGeom& g) {
+    const int64_t bytes = (int64_t)g.cps_x * g.cps_y * (g.nz_local + 2 * g.halo) * 3 * g.nmax * 4;
+    return bytes < ((int64_t)1 << 32);
+}
+
+// Run-time geometry -> template arguments.  f is a generic lambda; it reads its arguments' ::value.
+template <int N> using int_c = std::integral_constant<int, N>;
+template <class F>
+static void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// shift and energy (lanes per cell only): f(int_c<NSLOT>, bool_constant<OFF32>)
+template <class F>
+static void with_nslot(const DevGeom& g, bool off32, F&& f) {
+    with_bool(off32, [&](auto off) {
+        switch (g.nslot) {
+            case 8: f(int_c<8>{}, off); break;
+            case 16: f(int_c<16>{}, off); break;
+            case 32: f(int_c<32>{}, off); break;
+            default: f(int_c<64>{}, off); break;
+        }
+    });
+}
+// subsweep families: f(int_c<NSLOT>, int_c<NMC>, bool_constant<OFF32>); NMC = nmax as a constant
+// for the two common row lengths, 0 = read from the geometry
+template <class F>
+static void with_shape(const DevGeom& g, bool off32, F&& f) {
+    if (g.nmax == 16) with_bool(off32, [&](auto off) { f(int_c<16>{}, int_c<16>{}, off); });
+    else if (g.nmax == 32) with_bool(off32, [&](auto off) { f(int_c<32>{}, int_c<32>{}, off); });
+    else with_nslot(g, off32, [&](auto ns, auto off) { f(ns, int_c<0>{}, off); });
+}
+
+// The overflow launch after a main-capacity launch: the cells queued on ovf, at full capacity.
+// Untimed (no launch_k).  czs/stats1: the second plane of a two-plane launch (1/stats0 otherwise).
+template <int NSLOT, int NMC, bool OFF32, bool MIRROR>
+static void launch_overflow(const DevGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz, uint32_t sweep,
+                            unsigned long long* stats0, unsigned long long* stats1, int* ovf, int cz0, int czs,
+                            float* mirror, int mode, hipStream_t st) {
+    const int full = 27 * g.nmax;
+    if (subsweep_capacity(g) >= full) return;
+    hipLaunchKernelGGL((k_subsweep_fallback<NSLOT, NMC, OFF32, MIRROR>), dim3(fallback_blocks()),
+                       dim3(kWave * kSubWaves), lds_bytes(full), st, g, disk, n, ox, oy, oz, sweep, stats0, ovf, cz0,
+                       mirror, mode, czs, stats1);
+}
+
+// one cell per wave at the main capacity + overflow launch: the slab's boundary planes
 template <int NSLOT, int NMC, bool OFF32>
 static void launch_direct_t(const DevGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz, uint32_t sweep,
                             unsigned long long* stats, int* ovf, int cz0, int ncz, float* mirror, int mode,
-                            hipStream_t st, const LaunchTiming* tm);
+                            hipStream_t st, const LaunchTiming* tm) {
+    const dim3 grid((unsigned)((phase_cells(g, ncz) + kSubWaves - 1) / kSubWaves)), block(kWave * kSubWaves);
+    // PMC_BOUNDARY_FULL=1: the boundary plane at full capacity (27*nmax partners, 9.9 KiB of LDS per
+    // wave): nothing can overflow, so a phase is ONE launch -- no fallback launch on the exchange
+    // stream, whose chain (boundary phases -> exchange -> next run's boundary phases) is the sweep's
+    // critical path once the exchange takes xGMI time
+    static const bool bfull = env_cells("PMC_BOUNDARY_FULL", 0) == 1;
+    if (bfull && !mirror) {
+        launch_k(k_subsweep_full<NSLOT, NMC, OFF32, PMC_BOUNDARY_PB>, grid, block, lds_bytes(27 * g.nmax), st, tm, g,
+                 disk, n, ox, oy, oz, sweep, stats, cz0, ncz);
+        return;
+    }
+    launch_k(k_subsweep_direct<NSLOT, NMC, OFF32>, grid, block, lds_bytes(kMainCap), st, tm, g, disk, n, ox, oy, oz,
+             sweep, stats, subsweep_capacity(g), ovf, cz0, ncz, mirror, mode);
+    if (mirror) launch_overflow<NSLOT, NMC, OFF32, true>(g, disk, n, ox, oy, oz, sweep, stats, stats, ovf, cz0, 1, mirror, mode, st);
+    else launch_overflow<NSLOT, NMC, OFF32, false>(g, disk, n, ox, oy, oz, sweep, stats, stats, ovf, cz0, 1, nullptr, 0, st);
+}
 
+// two colour planes czs apart in one launch (k_subsweep_direct2), plane 1's counters to stats1
+template <int NSLOT, int NMC, bool OFF32>
+static void launch_direct2_t(const DevGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz, uint32_t sweep,
+                             unsigned long long* stats0, unsigned long long* stats1, int* ovf, int cz0, int czs,
+                             hipStream_t st, const LaunchTiming* tm) {
+    const dim3 grid((unsigned)((phase_cells(g, 2) + kSubWaves - 1) / kSubWaves)), block(kWave * kSubWaves);
+    launch_k(k_subsweep_direct2<NSLOT, NMC, OFF32>, grid, block, lds_bytes(kMainCap), st, tm, g, disk, n, ox, oy, oz,
+             sweep, stats0, stats1, subsweep_capacity(g), ovf, cz0, czs);
+    launch_overflow<NSLOT, NMC, OFF32, false>(g, disk, n, ox, oy, oz, sweep, stats0, stats1, ovf, cz0, czs, nullptr, 0, st);
+}
+
+// a colour phase of a whole box or of a chain's interior planes
 template <int NSLOT, int NMC, bool OFF32>
 static void launch_subsweep_t(const DevGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz,
                               uint32_t sweep, unsigned long long* stats, int* ovf, int cz0, int ncz,
                               hipStream_t st, const LaunchTiming* tm, bool solo) {
-    const int64_t total = (int64_t)(g.cps_x / 2) * (g.cps_y / 2) * ncz;
-    const int64_t waves = (total + PMC_CELLS_PER_WAVE - 1) / PMC_CELLS_PER_WAVE;
-    const int64_t blocks = (waves + kSubWaves - 1) / kSubWaves;
-    const int cap = subsweep_capacity(g);
-    const int full = 27 * g.nmax;
+    const int64_t total = phase_cells(g, ncz);
+    const dim3 block(kWave * kSubWaves);
     static const int64_t small_cells = env_cells("PMC_SMALL_LAUNCH", 8192);
     if (total <= small_cells) {   // one launch, one full-capacity cell per wave (k_subsweep_full)
-        const size_t lds_full = sizeof(float) * (size_t)lds_floats_per_wave(full) * kSubWaves;
-        launch_k(k_subsweep_full<NSLOT, NMC, OFF32>, dim3((unsigned)((total + kSubWaves - 1) / kSubWaves)),
-                 dim3(kWave * kSubWaves), lds_full, st, tm, g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz);
+        launch_k(k_subsweep_full<NSLOT, NMC, OFF32>, dim3((unsigned)((total + kSubWaves - 1) / kSubWaves)), block,
+                 lds_bytes(27 * g.nmax), st, tm, g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz);
         return;
     }
     // PMC_DIRECT_CELLS=<n> (default 0: off): phases of at most n cells as one cell per wave at the
@@ -2860,7 +2940,7 @@ static void launch_subsweep_t(const DevGeom& g, float* disk, const int16_t* n, i
         launch_direct_t<NSLOT, NMC, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, nullptr, 0, st, tm);
         return;
     }
-    size_t lds = sizeof(float) * (size_t)lds_floats_per_wave(kMainCap) * kSubWaves;
+    const int cap = subsweep_capacity(g);
     // Solo launches (nothing else on the GPU) of at most two rounds of the chip's wave slots (<= 32768
     // cells: 16384 two-cell waves) end in single-cell waves, 1/8 of each XCD's cells
     // (k_subsweep_mixed): config 2's phase -3.7% (profiles/r06m_mixed_tail_ab.txt).  Launches beside
@@ -2874,110 +2954,44 @@ static void launch_subsweep_t(const DevGeom& g, float* disk, const int16_t* n, i
         const int singles = (int)(mixed < per_xcd ? mixed : per_xcd);
         const int pair_waves = (per_xcd - singles) / 2;
         const int waves_xcd = pair_waves + (per_xcd - 2 * pair_waves);
-        launch_k(k_subsweep_mixed<NSLOT, NMC, OFF32>, dim3(8u * (unsigned)waves_xcd), dim3(kWave), lds, st, tm, g, disk,
-                 n, ox, oy, oz, sweep, stats, cap, ovf, cz0, ncz, per_xcd, pair_waves);
-    } else
-    launch_k(k_subsweep<NSLOT, NMC, OFF32>, dim3((unsigned)blocks), dim3(kWave * kSubWaves), lds, st, tm, g, disk, n,
-             ox, oy, oz, sweep, stats, cap, ovf, cz0, ncz);
-    if (cap < full) {
-        const size_t lds_full = sizeof(float) * (size_t)lds_floats_per_wave(full) * kSubWaves;
-        hipLaunchKernelGGL((k_subsweep_fallback<NSLOT, NMC, OFF32>), dim3(fallback_blocks()), dim3(kWave * kSubWaves), lds_full, st,
-                           g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, (float*)nullptr, 0, 1, stats);
+        launch_k(k_subsweep_mixed<NSLOT, NMC, OFF32>, dim3(8u * (unsigned)waves_xcd), dim3(kWave), lds_bytes(kMainCap),
+                 st, tm, g, disk, n, ox, oy, oz, sweep, stats, cap, ovf, cz0, ncz, per_xcd, pair_waves);
+    } else {
+        const int64_t waves = (total + PMC_CELLS_PER_WAVE - 1) / PMC_CELLS_PER_WAVE;
+        launch_k(k_subsweep<NSLOT, NMC, OFF32>, dim3((unsigned)((waves + kSubWaves - 1) / kSubWaves)), block,
+                 lds_bytes(kMainCap), st, tm, g, disk, n, ox, oy, oz, sweep, stats, cap, ovf, cz0, ncz);
     }
-}
-
-template <int NSLOT, int NMC, bool OFF32>
-static void launch_direct_t(const DevGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz, uint32_t sweep,
-                            unsigned long long* stats, int* ovf, int cz0, int ncz, float* mirror, int mode,
-                            hipStream_t st, const LaunchTiming* tm) {
-    const int64_t total = (int64_t)(g.cps_x / 2) * (g.cps_y / 2) * ncz;
-    const int64_t blocks = (total + kSubWaves - 1) / kSubWaves;   // one cell per wave
-    const int cap = subsweep_capacity(g);
-    const int full = 27 * g.nmax;
-    // PMC_BOUNDARY_FULL=1: the boundary plane at full capacity (27*nmax partners, 9.9 KiB of LDS per
-    // wave): nothing can overflow, so a phase is ONE launch -- no fallback launch on the exchange
-    // stream, whose chain (boundary phases -> exchange -> next run's boundary phases) is the sweep's
-    // critical path once the exchange takes xGMI time
-    static const bool bfull = env_cells("PMC_BOUNDARY_FULL", 0) == 1;
-    if (bfull && !mirror) {
-        const size_t lds_full = sizeof(float) * (size_t)lds_floats_per_wave(full) * kSubWaves;
-        launch_k(k_subsweep_full<NSLOT, NMC, OFF32, PMC_BOUNDARY_PB>, dim3((unsigned)blocks), dim3(kWave * kSubWaves),
-                 lds_full, st, tm, g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz);
-        return;
-    }
-    const size_t lds = sizeof(float) * (size_t)lds_floats_per_wave(kMainCap) * kSubWaves;
-    launch_k(k_subsweep_direct<NSLOT, NMC, OFF32>, dim3((unsigned)blocks), dim3(kWave * kSubWaves), lds, st, tm, g,
-             disk, n, ox, oy, oz, sweep, stats, cap, ovf, cz0, ncz, mirror, mode);
-    if (cap < full) {
-        const size_t lds_full = sizeof(float) * (size_t)lds_floats_per_wave(full) * kSubWaves;
-        if (mirror)
-            hipLaunchKernelGGL((k_subsweep_fallback<NSLOT, NMC, OFF32, true>), dim3(fallback_blocks()),
-                               dim3(kWave * kSubWaves), lds_full, st, g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0,
-                               mirror, mode, 1, stats);
-        else
-            hipLaunchKernelGGL((k_subsweep_fallback<NSLOT, NMC, OFF32>), dim3(fallback_blocks()),
-                               dim3(kWave * kSubWaves), lds_full, st, g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0,
-                               (float*)nullptr, 0, 1, stats);
-    }
+    launch_overflow<NSLOT, NMC, OFF32, false>(g, disk, n, ox, oy, oz, sweep, stats, stats, ovf, cz0, 1, nullptr, 0, st);
 }
 
 // Quirks R1/R2 (pmc.h): every colour phase through the full-capacity one-cell-per-wave kernel,
 // instantiated with the quirk bits (the corrected-semantics kernels are not touched by them)
-template <int NSLOT, int NMC, bool OFF32, int QK>
-static void launch_quirk_t(const DevGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz, uint32_t sweep,
-                           unsigned long long* stats, int cz0, int ncz, hipStream_t st, const LaunchTiming* tm) {
-    const int64_t total = (int64_t)(g.cps_x / 2) * (g.cps_y / 2) * ncz;
-    const int full = 27 * g.nmax;
-    const size_t lds_full = sizeof(float) * (size_t)lds_floats_per_wave(full) * kSubWaves;
-    launch_k(k_subsweep_full<NSLOT, NMC, OFF32, 0, QK>, dim3((unsigned)((total + kSubWaves - 1) / kSubWaves)),
-             dim3(kWave * kSubWaves), lds_full, st, tm, g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz);
-}
-template <bool OFF32, int QK>
-static void launch_quirk_q(const DevGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz, uint32_t sweep,
-                           unsigned long long* stats, int cz0, int ncz, hipStream_t st, const LaunchTiming* tm) {
-    if (g.nmax == 16) launch_quirk_t<16, 16, OFF32, QK>(g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm);
-    else if (g.nmax == 32) launch_quirk_t<32, 32, OFF32, QK>(g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm);
-    else if (g.nslot == 8) launch_quirk_t<8, 0, OFF32, QK>(g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm);
-    else if (g.nslot == 16) launch_quirk_t<16, 0, OFF32, QK>(g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm);
-    else if (g.nslot == 32) launch_quirk_t<32, 0, OFF32, QK>(g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm);
-    else launch_quirk_t<64, 0, OFF32, QK>(g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm);
-}
 constexpr uint32_t kQuirksRng = PMC_FLAG_QUIRK_R1 | PMC_FLAG_QUIRK_R2;
-template <bool OFF32>
-static void launch_quirk_n(const HostGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz, uint32_t sweep,
-                           unsigned long long* stats, int cz0, int ncz, hipStream_t st, const LaunchTiming* tm) {
+static void launch_quirk(const HostGeom& g, bool off32, float* disk, const int16_t* n, int ox, int oy, int oz,
+                         uint32_t sweep, unsigned long long* stats, int cz0, int ncz, hipStream_t st,
+                         const LaunchTiming* tm) {
     const DevGeom& kg = g;
-    switch (g.quirks & kQuirksRng) {
-        case PMC_FLAG_QUIRK_R1:
-            launch_quirk_q<OFF32, PMC_FLAG_QUIRK_R1>(kg, disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm); break;
-        case PMC_FLAG_QUIRK_R2:
-            launch_quirk_q<OFF32, PMC_FLAG_QUIRK_R2>(kg, disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm); break;
-        default:
-            launch_quirk_q<OFF32, kQuirksRng>(kg, disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm); break;
-    }
+    const dim3 grid((unsigned)((phase_cells(g, ncz) + kSubWaves - 1) / kSubWaves)), block(kWave * kSubWaves);
+    with_shape(g, off32, [&](auto ns, auto nmc, auto off) {
+        constexpr int NS = decltype(ns)::value, NMC = decltype(nmc)::value;
+        constexpr bool O = decltype(off)::value;
+        const uint32_t q = g.quirks & kQuirksRng;
+        const auto k = q == PMC_FLAG_QUIRK_R1   ? k_subsweep_full<NS, NMC, O, 0, PMC_FLAG_QUIRK_R1>
+                       : q == PMC_FLAG_QUIRK_R2 ? k_subsweep_full<NS, NMC, O, 0, PMC_FLAG_QUIRK_R2>
+                                                : k_subsweep_full<NS, NMC, O, 0, kQuirksRng>;
+        launch_k(k, grid, block, lds_bytes(27 * g.nmax), st, tm, kg, disk, n, ox, oy, oz, sweep, stats, cz0, ncz);
+    });
 }
 
-template <bool OFF32>
-static void launch_direct_n(const DevGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz, uint32_t sweep,
-                            unsigned long long* stats, int* ovf, int cz0, int ncz, float* mirror, int mode, hipStream_t st, const LaunchTiming* tm) {
-    if (g.nmax == 16) launch_direct_t<16, 16, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, mirror, mode, st, tm);
-    else if (g.nmax == 32) launch_direct_t<32, 32, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, mirror, mode, st, tm);
-    else if (g.nslot == 8) launch_direct_t<8, 0, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, mirror, mode, st, tm);
-    else if (g.nslot == 16) launch_direct_t<16, 0, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, mirror, mode, st, tm);
-    else if (g.nslot == 32) launch_direct_t<32, 0, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, mirror, mode, st, tm);
-    else launch_direct_t<64, 0, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, mirror, mode, st, tm);
-}
-
-template <bool OFF32>
-static void launch_subsweep_n(const DevGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz,
-                              uint32_t sweep, unsigned long long* stats, int* ovf, int cz0, int ncz,
-                              hipStream_t st, const LaunchTiming* tm, bool solo) {
-    if (g.nmax == 16) launch_subsweep_t<16, 16, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, st, tm, solo);
-    else if (g.nmax == 32) launch_subsweep_t<32, 32, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, st, tm, solo);
-    else if (g.nslot == 8) launch_subsweep_t<8, 0, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, st, tm, solo);
-    else if (g.nslot == 16) launch_subsweep_t<16, 0, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, st, tm, solo);
-    else if (g.nslot == 32) launch_subsweep_t<32, 0, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, st, tm, solo);
-    else launch_subsweep_t<64, 0, OFF32>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, st, tm, solo);
+// colour planes z = 2*cz + oz inside local planes [zl_begin, zl_end): the first cz and how many
+// (ncz <= 0: the range holds no plane of the colour)
+struct ColourPlanes {
+    int cz0, ncz;
+};
+static ColourPlanes colour_planes(int zl_begin, int zl_end, int oz, int nz_local) {
+    auto ceil_half = [](int v) { return v <= 0 ? 0 : (v + 1) / 2; };
+    const int cz0 = ceil_half(zl_begin - oz), cz1 = ceil_half(zl_end - oz), nczc = nz_local / 2;
+    return {cz0, (cz1 > nczc ? nczc : cz1) - cz0};
 }
 
 // a timed launch with nothing to visit (a chain whose planes hold no plane of the colour): its
@@ -2991,42 +3005,27 @@ static hipError_t skip_launch(hipStream_t st, const LaunchTiming* tm) {
     return hipSuccess;
 }
 
-hipError_t launch_subsweep_boundary(const HostGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz,
-                                    uint32_t sweep, unsigned long long* stats, int* ovf, int zl_begin, int zl_end,
-                                    float* mirror, int mirror_mode, hipStream_t st, const LaunchTiming* tm) {
-    auto ceil_half = [](int v) { return v <= 0 ? 0 : (v + 1) / 2; };
-    const int nczc = g.nz_local / 2;
-    int cz0 = ceil_half(zl_begin - oz), cz1 = ceil_half(zl_end - oz);
-    if (cz1 > nczc) cz1 = nczc;
-    if (cz1 <= cz0) return skip_launch(st, tm);
-    const int64_t bytes = (int64_t)g.cps_x * g.cps_y * (g.nz_local + 2 * g.halo) * 3 * g.nmax * 4;
+// colour planes [cz0, cz0 + ncz) the boundary way: one cell per wave (or the quirk kernels)
+static hipError_t launch_direct(const HostGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz,
+                                uint32_t sweep, unsigned long long* stats, int* ovf, int cz0, int ncz, float* mirror,
+                                int mode, hipStream_t st, const LaunchTiming* tm) {
     if (g.quirks & kQuirksRng) {   // (no mirror rows: pmc_slab_sweep turns the direct halo off with R1/R2)
         if (mirror) return hipErrorInvalidValue;
-        if (bytes < ((int64_t)1 << 32)) launch_quirk_n<true>(g, disk, n, ox, oy, oz, sweep, stats, cz0, cz1 - cz0, st, tm);
-        else launch_quirk_n<false>(g, disk, n, ox, oy, oz, sweep, stats, cz0, cz1 - cz0, st, tm);
-        return hipGetLastError();
-    }
-    if (bytes < ((int64_t)1 << 32)) launch_direct_n<true>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, cz1 - cz0, mirror, mirror_mode, st, tm);
-    else launch_direct_n<false>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, cz1 - cz0, mirror, mirror_mode, st, tm);
+        launch_quirk(g, disk_off32(g), disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm);
+    } else
+        with_shape(g, disk_off32(g), [&](auto ns, auto nmc, auto off) {
+            launch_direct_t<decltype(ns)::value, decltype(nmc)::value, decltype(off)::value>(
+                g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, mirror, mode, st, tm);
+        });
     return hipGetLastError();
 }
 
-template <int NSLOT, int NMC, bool OFF32>
-static void launch_direct2_t(const DevGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz, uint32_t sweep,
-                             unsigned long long* stats0, unsigned long long* stats1, int* ovf, int cz0, int czs,
-                             hipStream_t st, const LaunchTiming* tm) {
-    const int64_t total = 2 * (int64_t)(g.cps_x / 2) * (g.cps_y / 2);
-    const int64_t blocks = (total + kSubWaves - 1) / kSubWaves;
-    const int cap = subsweep_capacity(g);
-    const int full = 27 * g.nmax;
-    const size_t lds = sizeof(float) * (size_t)lds_floats_per_wave(kMainCap) * kSubWaves;
-    launch_k(k_subsweep_direct2<NSLOT, NMC, OFF32>, dim3((unsigned)blocks), dim3(kWave * kSubWaves), lds, st, tm, g,
-             disk, n, ox, oy, oz, sweep, stats0, stats1, cap, ovf, cz0, czs);
-    if (cap < full) {
-        const size_t lds_full = sizeof(float) * (size_t)lds_floats_per_wave(full) * kSubWaves;
-        hipLaunchKernelGGL((k_subsweep_fallback<NSLOT, NMC, OFF32>), dim3(fallback_blocks()), dim3(kWave * kSubWaves),
-                           lds_full, st, g, disk, n, ox, oy, oz, sweep, stats0, ovf, cz0, (float*)nullptr, 0, czs, stats1);
-    }
+hipError_t launch_subsweep_boundary(const HostGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz,
+                                    uint32_t sweep, unsigned long long* stats, int* ovf, int zl_begin, int zl_end,
+                                    float* mirror, int mirror_mode, hipStream_t st, const LaunchTiming* tm) {
+    const ColourPlanes p = colour_planes(zl_begin, zl_end, oz, g.nz_local);
+    if (p.ncz <= 0) return skip_launch(st, tm);
+    return launch_direct(g, disk, n, ox, oy, oz, sweep, stats, ovf, p.cz0, p.ncz, mirror, mirror_mode, st, tm);
 }
 
 hipError_t launch_subsweep_planes2(const DevGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz,
@@ -3037,19 +3036,10 @@ hipError_t launch_subsweep_planes2(const DevGeom& g, float* disk, const int16_t*
     for (int zl : {zl0, zl1})
         if (zl - 1 < -g.halo || zl + 1 > g.nz_local - 1 + g.halo) return hipErrorInvalidValue;
     const int cz0 = (zl0 - oz) >> 1, czs = (zl1 - zl0) >> 1;
-    const int64_t bytes = (int64_t)g.cps_x * g.cps_y * (g.nz_local + 2 * g.halo) * 3 * g.nmax * 4;
-    const bool off32 = bytes < ((int64_t)1 << 32);
-    auto go = [&](auto off) {
-        constexpr bool O = decltype(off)::value;
-        if (g.nmax == 16) launch_direct2_t<16, 16, O>(g, disk, n, ox, oy, oz, sweep, stats0, stats1, ovf, cz0, czs, st, tm);
-        else if (g.nmax == 32) launch_direct2_t<32, 32, O>(g, disk, n, ox, oy, oz, sweep, stats0, stats1, ovf, cz0, czs, st, tm);
-        else if (g.nslot == 8) launch_direct2_t<8, 0, O>(g, disk, n, ox, oy, oz, sweep, stats0, stats1, ovf, cz0, czs, st, tm);
-        else if (g.nslot == 16) launch_direct2_t<16, 0, O>(g, disk, n, ox, oy, oz, sweep, stats0, stats1, ovf, cz0, czs, st, tm);
-        else if (g.nslot == 32) launch_direct2_t<32, 0, O>(g, disk, n, ox, oy, oz, sweep, stats0, stats1, ovf, cz0, czs, st, tm);
-        else launch_direct2_t<64, 0, O>(g, disk, n, ox, oy, oz, sweep, stats0, stats1, ovf, cz0, czs, st, tm);
-    };
-    if (off32) go(std::true_type{});
-    else go(std::false_type{});
+    with_shape(g, disk_off32(g), [&](auto ns, auto nmc, auto off) {
+        launch_direct2_t<decltype(ns)::value, decltype(nmc)::value, decltype(off)::value>(
+            g, disk, n, ox, oy, oz, sweep, stats0, stats1, ovf, cz0, czs, st, tm);
+    });
     return hipGetLastError();
 }
 
@@ -3062,38 +3052,25 @@ hipError_t launch_subsweep_plane(const HostGeom& g, float* disk, const int16_t* 
     // the visit reads planes zl - 1 .. zl + 1, which must be stored
     if (g.halo && (zl - 1 < -g.halo || zl + 1 > g.nz_local - 1 + g.halo)) return hipErrorInvalidValue;
     const int cz = (zl - oz) >> 1;   // arithmetic shift: floor, so zl = -1 (oz = 1) gives -1
-    const int64_t bytes = (int64_t)g.cps_x * g.cps_y * (g.nz_local + 2 * g.halo) * 3 * g.nmax * 4;
-    if (g.quirks & kQuirksRng) {
-        if (bytes < ((int64_t)1 << 32)) launch_quirk_n<true>(g, disk, n, ox, oy, oz, sweep, stats, cz, 1, st, tm);
-        else launch_quirk_n<false>(g, disk, n, ox, oy, oz, sweep, stats, cz, 1, st, tm);
-        return hipGetLastError();
-    }
-    if (bytes < ((int64_t)1 << 32)) launch_direct_n<true>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz, 1, nullptr, 0, st, tm);
-    else launch_direct_n<false>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz, 1, nullptr, 0, st, tm);
-    return hipGetLastError();
+    return launch_direct(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz, 1, nullptr, 0, st, tm);
 }
 
 hipError_t launch_subsweep(const HostGeom& g, float* disk, const int16_t* n, int ox, int oy, int oz,
                            uint32_t sweep, unsigned long long* stats, int* ovf, int zl_begin, int zl_end,
                            hipStream_t st, const LaunchTiming* tm, bool solo) {
-    // colour planes z = 2*cz + oz inside [zl_begin, zl_end)
-    auto ceil_half = [](int v) { return v <= 0 ? 0 : (v + 1) / 2; };
-    const int nczc = g.nz_local / 2;
-    int cz0 = ceil_half(zl_begin - oz), cz1 = ceil_half(zl_end - oz);
-    if (cz1 > nczc) cz1 = nczc;
-    if (cz1 <= cz0) return skip_launch(st, tm);
-    const int ncz = cz1 - cz0;
-    // 32-bit byte offsets when the disk buffer is below 4 GiB (every single-GPU 256^3 config)
-    // (test hook: PMC_FORCE_ADDR64 takes the 64-bit path for any size)
+    const ColourPlanes p = colour_planes(zl_begin, zl_end, oz, g.nz_local);
+    if (p.ncz <= 0) return skip_launch(st, tm);
+    // test hook: PMC_FORCE_ADDR64 takes the 64-bit path for any size
     static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;
-    const int64_t bytes = (int64_t)g.cps_x * g.cps_y * (g.nz_local + 2 * g.halo) * 3 * g.nmax * 4;
+    const bool off32 = !force64 && disk_off32(g);
     if (g.quirks & kQuirksRng) {
-        if (!force64 && bytes < ((int64_t)1 << 32)) launch_quirk_n<true>(g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm);
-        else launch_quirk_n<false>(g, disk, n, ox, oy, oz, sweep, stats, cz0, ncz, st, tm);
+        launch_quirk(g, off32, disk, n, ox, oy, oz, sweep, stats, p.cz0, p.ncz, st, tm);
         return hipGetLastError();
     }
-    if (!force64 && bytes < ((int64_t)1 << 32)) launch_subsweep_n<true>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, st, tm, solo);
-    else launch_subsweep_n<false>(g, disk, n, ox, oy, oz, sweep, stats, ovf, cz0, ncz, st, tm, solo);
+    with_shape(g, off32, [&](auto ns, auto nmc, auto off) {
+        launch_subsweep_t<decltype(ns)::value, decltype(nmc)::value, decltype(off)::value>(
+            g, disk, n, ox, oy, oz, sweep, stats, ovf, p.cz0, p.ncz, st, tm, solo);
+    });
     return hipGetLastError();
 }
 
@@ -3112,8 +3089,7 @@ hipError_t launch_sweep_small(const HostGeom& g, float* disk0, int16_t* n0, floa
     const int P = small_sweep_participants(g);
     if (P == 0) return hipErrorInvalidValue;
     const size_t lds = sizeof(float) * (size_t)lds_floats_per_wave(27 * 16);
-    const bool off32 = (int64_t)g.cps_x * g.cps_y * g.cps_z * 3 * g.nmax * 4 < ((int64_t)1 << 32);
-    if (!off32) return hipErrorInvalidValue;
+    if (!disk_off32(g)) return hipErrorInvalidValue;   // (the kernel has the 32-bit form only)
     for (int done = 0; done < count;) {
         SmallPlans sp;
         std::memset(&sp, 0, sizeof(sp));
@@ -3168,8 +3144,7 @@ hipError_t launch_shift_planes(const HostGeom& g, const float* din, const int16_
     // profiles/r04q_shift_off32_ab.txt); with the packed layout 0.146-0.147 against 0.151-0.153 ms
     // (profiles/r05h_shift_variants_ab.txt), so it is the default now
     static const bool off32_env = env_cells("PMC_SHIFT_OFF32", 1) != 0;
-    const int64_t bytes = (int64_t)g.cps_x * g.cps_y * (g.nz_local + 2 * g.halo) * 3 * g.nmax * 4;
-    const bool off32 = off32_env && bytes < ((int64_t)1 << 32);
+    const bool off32 = off32_env && disk_off32(g);
     // PMC_SHIFT_RUN (default 1): runs of kShiftRun cells along the shift axis per lane group (k_shift_run)
     static const bool run_env = env_cells("PMC_SHIFT_RUN", 1) != 0;
     const int nzr = zl_end - zl_begin;
@@ -3179,28 +3154,15 @@ hipError_t launch_shift_planes(const HostGeom& g, const float* din, const int16_
     const int64_t lgs = kShiftThreads / g.nslot;
     const dim3 rgrid((unsigned)((runs + lgs - 1) / lgs));
     const DevGeom& kg = g;   // the kernels' argument block
-    auto go = [&](auto ns, auto s1) {
-        constexpr int NS = decltype(ns)::value;
-        constexpr bool S1 = decltype(s1)::value;
-        if (run_env) {
-            if (off32) launch_k(k_shift_run<NS, kShiftRun, 1, S1>, rgrid, block, 0, st, tm, kg, din, nin, dout, nout, f, d, flags, z0, nzr);
-            else launch_k(k_shift_run<NS, kShiftRun, 0, S1>, rgrid, block, 0, st, tm, kg, din, nin, dout, nout, f, d, flags, z0, nzr);
-            return;
-        }
-        if (off32) launch_k(k_shift<NS, U, 1, S1>, grid, block, 0, st, tm, kg, din, nin, dout, nout, f, d, flags, z0);
-        else launch_k(k_shift<NS, U, 0, S1>, grid, block, 0, st, tm, kg, din, nin, dout, nout, f, d, flags, z0);
-    };
     // quirk S1 (pmc.h): the integer offset -- its own instantiations, the default kernels unchanged
-    auto by_slot = [&](auto s1) {
-        switch (g.nslot) {
-            case 8: go(std::integral_constant<int, 8>{}, s1); break;
-            case 16: go(std::integral_constant<int, 16>{}, s1); break;
-            case 32: go(std::integral_constant<int, 32>{}, s1); break;
-            default: go(std::integral_constant<int, 64>{}, s1); break;
-        }
-    };
-    if (g.quirks & PMC_FLAG_QUIRK_S1) by_slot(std::true_type{});
-    else by_slot(std::false_type{});
+    with_bool((g.quirks & PMC_FLAG_QUIRK_S1) != 0, [&](auto s1) {
+        with_nslot(g, off32, [&](auto ns, auto off) {
+            constexpr int NS = decltype(ns)::value, O = decltype(off)::value;
+            constexpr bool S1 = decltype(s1)::value;
+            if (run_env) launch_k(k_shift_run<NS, kShiftRun, O, S1>, rgrid, block, 0, st, tm, kg, din, nin, dout, nout, f, d, flags, z0, nzr);
+            else launch_k(k_shift<NS, U, O, S1>, grid, block, 0, st, tm, kg, din, nin, dout, nout, f, d, flags, z0);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -3240,9 +3202,6 @@ hipError_t launch_energy(const DevGeom& g, const float* disk, const int16_t* n,
     const size_t lds = sizeof(float) * (3 * 27 * (size_t)g.nmax + kEnergyRing + 32);
     dim3 grid((unsigned)((total + kEnergyCells - 1) / kEnergyCells)), block(kWave);
     const uint32_t tc = (uint32_t)total;
-    // 32-bit byte offsets below 4 GiB of disk (every single-GPU 256^3 box), else element offsets
-    const int64_t bytes = (int64_t)g.cps_x * g.cps_y * (g.nz_local + 2 * g.halo) * 3 * g.nmax * 4;
-    const bool off32 = bytes < ((int64_t)1 << 32);
     static const bool legacy = [] {
         const char* v = std::getenv("PMC_ENERGY_LEGACY");
         return v && std::atoi(v) == 1;
@@ -3271,24 +3230,19 @@ hipError_t launch_energy(const DevGeom& g, const float* disk, const int16_t* n,
     const bool per_cell = legacy || 14 * g.nmax > kEList;
     const unsigned seg_total = (unsigned)energy_segments(g);
     const dim3 grid_q(seg_total < 8192u ? (seg_total > 0u ? seg_total : 1u) : 8192u);
-    auto go = [&](auto k0, auto k1, auto k2, auto kr) {
+    with_nslot(g, disk_off32(g), [&](auto ns, auto off) {   // (off32 false: element offsets)
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
         if (per_cell) {
-            hipLaunchKernelGGL(k0, grid, block, lds, st, g, disk, n, acc, tc, segq, div_nsx);
+            hipLaunchKernelGGL((k_energy<NS, O, 0>), grid, block, lds, st, g, disk, n, acc, tc, segq, div_nsx);
             return;
         }
-        hipLaunchKernelGGL(kr, grid_rows, block, lds_rows, st, g, disk, n, acc, segq, div_nsx, div_cy, cap);
-        hipLaunchKernelGGL(k1, dim3((unsigned)((n_edge + kEdgeCells - 1) / kEdgeCells)), block, lds, st, g, disk, n,
-                           acc, (uint32_t)n_edge, segq, div_nsx);
-        hipLaunchKernelGGL(k2, grid_q, block, lds, st, g, disk, n, acc, tc, segq, div_nsx);
-    };
-#define PMC_ENERGY_GO(NS, O32) go(k_energy<NS, O32, 0>, k_energy<NS, O32, 1>, k_energy<NS, O32, 2>, k_energy_rows<NS, O32>)
-    switch (g.nslot) {
-        case 8: off32 ? PMC_ENERGY_GO(8, true) : PMC_ENERGY_GO(8, false); break;
-        case 16: off32 ? PMC_ENERGY_GO(16, true) : PMC_ENERGY_GO(16, false); break;
-        case 32: off32 ? PMC_ENERGY_GO(32, true) : PMC_ENERGY_GO(32, false); break;
-        default: off32 ? PMC_ENERGY_GO(64, true) : PMC_ENERGY_GO(64, false); break;
-    }
-#undef PMC_ENERGY_GO
+        hipLaunchKernelGGL((k_energy_rows<NS, O>), grid_rows, block, lds_rows, st, g, disk, n, acc, segq, div_nsx,
+                           div_cy, cap);
+        hipLaunchKernelGGL((k_energy<NS, O, 1>), dim3((unsigned)((n_edge + kEdgeCells - 1) / kEdgeCells)), block, lds,
+                           st, g, disk, n, acc, (uint32_t)n_edge, segq, div_nsx);
+        hipLaunchKernelGGL((k_energy<NS, O, 2>), grid_q, block, lds, st, g, disk, n, acc, tc, segq, div_nsx);
+    });
     return hipGetLastError();
 }
 

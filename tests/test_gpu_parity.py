@@ -191,6 +191,31 @@ def test_full_sweeps_nmax_parity(pmc, oracle, nmax):
     assert r["accepted"] == o["accepted"] and r["trials"] == o["trials"], (r, o)
 
 
+@pytest.mark.parametrize("flags", [0, 2 | 4 | 8])   # corrected semantics; PMC_FLAG_QUIRK_R1 | _R2 | _S1
+def test_full_sweeps_nmax40_parity(pmc, oracle, flags):
+    """nmax 40 (33-64: 64 lanes per cell, row length read from the geometry -- the <64, 0> kernels):
+    an 8^3 box of 2400 lattice particles (the oracle alone runs it with no overflow), three whole
+    sweeps whose plans shift along z, x and y, then the energy.  With the quirk flags the phases run
+    k_subsweep_full<64, 0, .., QK> and the shifts k_shift_run<64, .., S1>.  Tolerance: none."""
+    cps, nmax, atoms, count = 8, 40, 2400, 3
+    first = next(s for s in range(400)
+                 if len({oracle.sweep_plan(1234, s + k, 2.5, flags)[1] for k in range(count)}) == 3)
+    ctx = _ctx(pmc, cps, nmax=nmax, flags=flags)
+    ctx.init_lattice(atoms)
+    r = ctx.start(first, count)
+    st = _ostate(oracle, cps, nmax=nmax, flags=flags)
+    assert st.init_lattice(atoms) == 0
+    assert st.run(first, count) == 0
+    _assert_same(oracle, ctx, st, nmax)
+    o = st.stats.as_dict()
+    for k in ("de_fixed", "accepted", "trials", "evaluated"):
+        assert r[k] == o[k], k
+    assert r["e_final"] == st.energy()
+    assert ctx.energy() == st.energy()
+    assert ctx.error_flags() == 0
+    ctx.close()
+
+
 def test_full_sweeps_parity_16(pmc, oracle):
     ctx = _ctx(pmc, 16)
     ctx.init_lattice(10_000)
