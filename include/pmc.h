@@ -330,6 +330,22 @@ int pmc_run_small(pmc_ctx* ctx, uint32_t first_sweep, int count);
  * must be flushed first after pmc_slab_sweep (pmc_slab_finish): a z shift's halo plane may still be
  * pending, and that flush is collective, so pmc_energy refuses (PMC_ERR_ARG) instead of doing it. */
 int pmc_energy(pmc_ctx* ctx, double* e_out);
+/* Pair observables of the owned cells' particles: the virial sum and the g(r) histogram over
+ * ORDERED pairs (i in an owned cell, j in its 27-cell stencil, halo cells as partners only), defined
+ * bit for bit in pmc_pairobs.h.  The reference has neither (its only observable is calc_energy,
+ * kernel.cu:452-470).  h_hist is a HOST pointer to nbins counters: bin b counts the pairs inside the
+ * cutoff with b * r_max / nbins <= r < (b + 1) * r_max / nbins (each unordered pair twice).
+ * PMC_ERR_ARG for a null pointer, nbins outside 1..512, r_max not finite, <= 0 or > w, and for a
+ * slab context with a pending deferred z exchange (pmc_slab_finish first, as for pmc_energy).  Runs
+ * on the context stream and synchronises; state, statistics and error flags are left unchanged.
+ * There is no cross-rank reduction: every output is an integer sum, so the per-context results of a
+ * slab run are exactly additive and the caller sums them over the ranks. */
+typedef struct pmc_pair_obs {
+    int64_t virial_fixed;  /* sum over ordered pairs of fixed(v), 2^-32 units; W = 12 * this / 2^32 */
+    int64_t pairs;         /* ordered pairs with r2 <= rc2 */
+    int64_t particles;     /* particles in owned cells */
+} pmc_pair_obs;
+int pmc_pair_observables(pmc_ctx* ctx, float r_max, int nbins, uint64_t* h_hist, pmc_pair_obs* out);
 /* Read and optionally reset the accumulated subsweep statistics (synchronises). */
 int pmc_stats_read(pmc_ctx* ctx, pmc_stats* out, int reset);
 /* Device error flags (bit 0: shift overflow, bit 1: assign overflow, bit 2: assign range, bits 3-4:

@@ -19,8 +19,11 @@
 
 #include "pmc_internal.h"
 #include "../../include/pmc_detmath.h"
+#include "../../include/pmc_pairobs.h"
 
 using namespace pmc;
+
+static_assert(kPairObsMaxBins == PMC_PAIROBS_MAX_BINS, "pair observables: bin cap");
 
 struct pmc_slab;   // multi-GPU slab driver state (pmc_slab_init)
 
@@ -36,6 +39,7 @@ struct pmc_ctx {
     unsigned long long* stats = nullptr;   // kStatCounters * kStatSlots
     unsigned long long* eacc = nullptr;    // kStatSlots (energy)
     int* segq = nullptr;                   // energy: queue of row segments over the staging capacity
+    unsigned long long* pobs = nullptr;    // pair observables: accumulator copies (allocated on first use)
     uint32_t* flags = nullptr;
     int* ovf = nullptr;                    // subsweep overflow queue (1 + cells per colour)
     int* ovf_aux = nullptr;                // second queue: launches on a caller stream (pmc_phase_range_on)
@@ -406,6 +410,7 @@ void pmc_destroy(pmc_ctx* c) {
     if (c->stats) (void)hipFree(c->stats);
     if (c->eacc) (void)hipFree(c->eacc);
     if (c->segq) (void)hipFree(c->segq);
+    if (c->pobs) (void)hipFree(c->pobs);
     if (c->flags) (void)hipFree(c->flags);
     if (c->ovf) (void)hipFree(c->ovf);
     if (c->ovf_aux) (void)hipFree(c->ovf_aux);
@@ -755,6 +760,35 @@ int pmc_energy(pmc_ctx* c, double* e_out) {
     int64_t f = 0;
     if (int rc = energy_fixed(c, &f)) return rc;
     *e_out = (double)f / PMC_FIX_SCALE * 0.5;
+    return PMC_OK;
+}
+
+int pmc_pair_observables(pmc_ctx* c, float r_max, int nbins, uint64_t* h_hist, pmc_pair_obs* out) {
+    if (!c || !h_hist || !out) return fail(PMC_ERR_ARG, "bad argument");
+    if (nbins < 1 || nbins > PMC_PAIROBS_MAX_BINS) return fail(PMC_ERR_ARG, "pmc_pair_observables: nbins must be in 1..512");
+    if (!std::isfinite(r_max) || !(r_max > 0.0f) || r_max > c->P.w)
+        return fail(PMC_ERR_ARG, "pmc_pair_observables: r_max must be finite, > 0 and <= w");
+    // the kernel reads both halos, as the energy does (energy_fixed)
+    if (slab_pending_zdir(c))
+        return fail(PMC_ERR_ARG, "pmc_pair_observables: a slab halo exchange is pending (call pmc_slab_finish first)");
+    if (int rj = slab_join(c)) return rj;
+    const size_t per = (size_t)kPairObsHead + (size_t)nbins;
+    if (!c->pobs)
+        PMC_HIP(hipMalloc(&c->pobs, sizeof(unsigned long long) * kPairObsCopies * (kPairObsHead + kPairObsMaxBins)));
+    PMC_HIP(hipMemsetAsync(c->pobs, 0, sizeof(unsigned long long) * kPairObsCopies * per, c->stream));
+    hipError_t e = launch_pairobs(c->G, c->disk[c->cur], c->n[c->cur], c->pobs, pmc_pairobs_rmax2(r_max),
+                                  pmc_pairobs_bscale(r_max, nbins), nbins, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "pair observables launch");
+    std::vector<unsigned long long> h((size_t)kPairObsCopies * per);
+    PMC_HIP(hipMemcpyAsync(h.data(), c->pobs, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    std::vector<unsigned long long> s(per, 0ull);
+    for (int k = 0; k < kPairObsCopies; ++k)
+        for (size_t i = 0; i < per; ++i) s[i] += h[(size_t)k * per + i];
+    out->virial_fixed = (int64_t)s[0];
+    out->pairs = (int64_t)s[1];
+    out->particles = (int64_t)s[2];
+    for (int b = 0; b < nbins; ++b) h_hist[b] = (uint64_t)s[(size_t)kPairObsHead + (size_t)b];
     return PMC_OK;
 }
 

@@ -152,6 +152,15 @@ hipError_t launch_assign(const DevGeom& g, const float* r, int64_t n_atoms, floa
 size_t energy_segments(const DevGeom& g);
 hipError_t launch_energy(const DevGeom& g, const float* disk, const int16_t* n,
                          unsigned long long* acc, int* segq, hipStream_t st);
+// pair observables (k_pairobs): acc holds kPairObsCopies accumulator copies of kPairObsHead + nbins
+// counters each ([0] virial sum, [1] ordered pairs in the cutoff, [2] owned particles, then the
+// histogram), zeroed on st before the call; the host sums the copies
+constexpr int kPairObsCopies = 32;
+constexpr int kPairObsHead = 3;
+constexpr int kPairObsMaxBins = 512;   // PMC_PAIROBS_MAX_BINS
+static_assert((kPairObsCopies & (kPairObsCopies - 1)) == 0, "accumulator copies: a power of two");
+hipError_t launch_pairobs(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc,
+                          float rmax2, float bscale, int nbins, hipStream_t st);
 // the cells of one colour of one plane: mode 0 plane -> packed buffer, 1 packed -> plane,
 // 2 plane -> plane; (cps_x/2)*(cps_y/2)*3*nmax floats
 hipError_t launch_colour_rows(const DevGeom& g, const float* src, float* dst, int colour, int mode, hipStream_t st);

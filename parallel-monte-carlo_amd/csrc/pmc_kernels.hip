@@ -25,6 +25,7 @@
 
 #include "pmc_internal.h"
 #include "../../include/pmc_detmath.h"
+#include "../../include/pmc_pairobs.h"
 
 namespace pmc {
 
@@ -2457,6 +2458,254 @@ __global__ __launch_bounds__(kWave) void k_energy_rows(DevGeom g, const float* _
 }
 
 // ------------------------------------------------------------------------------------------
+// pair observables (include/pmc_pairobs.h): virial sum and g(r) histogram over ORDERED pairs, the
+// full directed 27-cell shell of every owned cell (orc_energy's walk; no half shell).  k_energy's
+// per-cell form: the stencil on lanes 0-26, slots [0, 8) of the occupied stencil cells loaded in
+// four passes of eight cells (the next cell's while this cell's pairs run), the fuller cells' slots
+// [8, n) in chunks of eight after them, every partner but the own cell's through the pmc_box_d2
+// filter (r_max <= w: a dropped partner is beyond the cutoff of every own particle) into LDS; then
+// each own particle against 64-partner blocks, the in-cutoff pairs compacted through an LDS ring
+// and only those evaluated (virial term, sqrt, bin).  A fixed grid of waves strides over runs of
+// kPairObsRun cells; a wave keeps a private u32 histogram in LDS (returnless ds_add_u32; its counts
+// stay below 2^32, launch_pairobs), the virial sum per lane and the pair / particle counts in
+// SGPRs, and flushes once, after its last cell, with 64-bit global atomics into one of
+// kPairObsCopies accumulator copies ([virial, pairs, particles, hist[nbins]] each) the host sums.
+// Integer sums only: exact in any order, equal to tests/pairobs_ref.c bit for bit.
+// ------------------------------------------------------------------------------------------
+constexpr int kPairObsRun = 8;      // consecutive cells per wave and stride step
+constexpr int kPairObsRing = 128;   // ring of in-cutoff r2 values
+
+struct PairObsStencil {
+    int kc;            // storage cell (lanes < 27)
+    float sx, sy, sz;  // periodic image
+    int cnt;           // particles, clamped to [0, nmax]; 0 on lanes >= 27
+    int x, y, zg;      // the cell (wave-uniform): its box filters the staged partners
+};
+
+__device__ __forceinline__ PairObsStencil pairobs_stencil(const DevGeom& g, const int16_t* __restrict__ ncnt,
+                                                          uint32_t t) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t q1 = udiv_magic(t, g.div_cx);          // t / cps_x
+    const uint32_t zq = udiv_magic(t, g.div_plane);       // t / (cps_x * cps_y)
+    const int x = (int)(t - q1 * (uint32_t)g.cps_x);
+    const int zl = (int)zq;
+    const int y = (int)(q1 - zq * (uint32_t)g.cps_y);
+    const int k = lane < 27 ? lane : 0;
+    // lane k = 9*hx + 3*hy + hz, h = 0, 1, 2 -> offset 0, -1, +1 (get_neighbors order, own cell first)
+    const int dx = (int)bit_of(kStencilPos[0], k) - (int)bit_of(kStencilNeg[0], k);
+    const int dy = (int)bit_of(kStencilPos[1], k) - (int)bit_of(kStencilNeg[1], k);
+    const int dz = (int)bit_of(kStencilPos[2], k) - (int)bit_of(kStencilNeg[2], k);
+    const int nx0 = x + dx, ny0 = y + dy, zg = g.z0 + zl + dz, nz0 = zl + dz;
+    const int nx = nx0 + (nx0 < 0 ? g.cps_x : 0) - (nx0 >= g.cps_x ? g.cps_x : 0);
+    const int ny = ny0 + (ny0 < 0 ? g.cps_y : 0) - (ny0 >= g.cps_y ? g.cps_y : 0);
+    PairObsStencil e;
+    e.x = x;
+    e.y = y;
+    e.zg = g.z0 + zl;
+    e.sx = nx0 < 0 ? -g.Lx : (nx0 >= g.cps_x ? g.Lx : 0.0f);
+    e.sy = ny0 < 0 ? -g.Ly : (ny0 >= g.cps_y ? g.Ly : 0.0f);
+    e.sz = zg < 0 ? -g.Lz : (zg >= g.cps_z ? g.Lz : 0.0f);
+    // slab: halo planes are storage planes (partners only); whole box: periodic wrap
+    const int nzl = g.halo ? nz0 : nz0 + (nz0 < 0 ? g.cps_z : 0) - (nz0 >= g.cps_z ? g.cps_z : 0);
+    e.kc = nx + g.cps_x * (ny + g.cps_y * (nzl + g.halo));
+    int cnt = lane < 27 ? (int)ncnt[e.kc] : 0;
+    cnt = cnt < 0 ? 0 : (cnt > g.nmax ? g.nmax : cnt);   // (a valid state never clamps: LDS capacity 27 * nmax)
+    e.cnt = cnt;
+    return e;
+}
+
+template <int NSLOT, bool OFF32>
+__global__ __launch_bounds__(kWave) void k_pairobs(DevGeom g, const float* __restrict__ disk,
+                                                   const int16_t* __restrict__ ncnt,
+                                                   unsigned long long* __restrict__ acc, uint32_t total_cells,
+                                                   float rmax2, float bscale, int nbins) {
+    extern __shared__ __attribute__((aligned(16))) float psm[];
+    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
+    constexpr int CPP = kWave / HS;    // cells per staging pass
+    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
+    using DA = DiskAddr<OFF32>;
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int cap = 27 * nm;
+    float* ex_ = psm;
+    float* ey_ = psm + cap;
+    float* ez_ = psm + 2 * cap;
+    float* ring = psm + 3 * cap;
+    int* inv_l = (int*)(ring + kPairObsRing);      // list entry -> stencil lane (32 ints)
+    unsigned* hist = (unsigned*)(inv_l + 32);      // nbins counters of this wave
+    const int p = lane % HS;
+    const int ee = lane / HS;
+    const float rc2 = g.rc2;
+    long long sum = 0;                             // per lane
+    unsigned long long n_pairs = 0, n_part = 0;    // wave-uniform
+    for (int b = lane; b < nbins; b += kWave) hist[b] = 0u;
+    if (lane < 32) inv_l[lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+
+    // rows of the cell in flight: slots [0, HS) of its occupied stencil cells (own cell: entry 0 when
+    // occupied), in registers
+    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
+    bool vact[NPMAX];
+    int ncells = 0;
+    auto issue_rows = [&](const PairObsStencil& st) {
+        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
+        ncells = __popcll(mo);
+        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int q = 0; q < NPMAX; ++q) {
+            const int e = q * CPP + ee;
+            const int src = inv_l[e < ncells ? e : 0];
+            const int c_cnt = __shfl(st.cnt, src);
+            const int c_idx = __shfl(st.kc, src);
+            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
+            vact[q] = e < ncells && p < c_cnt;
+            vx[q] = vy[q] = vz[q] = 0.0f;
+            if (vact[q]) {
+                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
+                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
+                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
+                vy[q] = vy[q] + isy;
+                vz[q] = vz[q] + isz;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
+    };
+
+    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
+    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
+        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
+        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
+        issue_rows(cur);
+        PairObsStencil nxt = cur;
+        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
+        for (int c = 0; c < ncl; ++c) {
+            // ---- stage cell c: own particles first (lanes of list entry 0 and the own chunks), then
+            //      the filtered partners
+            float blo[3], bhi[3];
+            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
+            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
+            int S = 0;
+            auto put = [&](bool act, float ux, float uy, float uz) {
+                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+                if (act) {
+                    const int dst = S + mbcnt64(am);
+                    ex_[dst] = ux;
+                    ey_[dst] = uy;
+                    ez_[dst] = uz;
+                }
+                S += __popcll(am);
+            };
+            // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles
+            auto chunks = [&](unsigned long long mg, bool filter) {
+                if constexpr (NSLOT > HS) {
+                    for (int s0 = HS; s0 < nm; s0 += HS) {
+                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
+                        while (ov) {
+                            int ks = 0, nc = 0;
+                            for (; nc < CPP && ov; ++nc) {
+                                const int kb = (int)__builtin_ctzll(ov);
+                                ov &= ov - 1ull;
+                                ks = ee == nc ? kb : ks;
+                            }
+                            const int c_cnt = __shfl(cur.cnt, ks);
+                            const int c_idx = __shfl(cur.kc, ks);
+                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
+                            const int ps = s0 + p;
+                            const bool act = ee < nc && ps < c_cnt;
+                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+                            if (act) {
+                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
+                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+                                ux = ux + isx;
+                                uy = uy + isy;
+                                uz = uz + isz;
+                            }
+                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz);
+                        }
+                    }
+                }
+            };
+            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
+            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
+            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0]);             // own slots [0, HS)
+            chunks(1ull, false);                                          // own slots [HS, n)
+#pragma unroll
+            for (int q = 0; q < NPMAX; ++q) {
+                const int e = q * CPP + ee;
+                if (q * CPP < ncells) put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q]);
+            }
+            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            // ---- the next cell's rows go out now and arrive while this cell's pairs run
+            if (c + 1 < ncl) {
+                cur = nxt;
+                issue_rows(cur);
+                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
+            }
+            n_part += (unsigned long long)n_own;
+            if (n_own == 0) continue;
+            // ---- ordered pairs (i, j): lane j holds staged partner j (blocks of 64), own particle
+            //      i (staged first: lane i of block 0) broadcast by readlane; j == i skipped
+            constexpr int RM = kPairObsRing - 1;
+            int head = 0, C = 0;   // ring: entries [head, head + C) mod kPairObsRing
+            auto drain = [&](int lim) {
+                if (lane < lim) {
+                    const float r2 = ring[(head + lane) & RM];
+                    sum += pmc_to_fixed_f32(pmc_virial_term(r2));
+                    if (r2 < rmax2)
+                        (void)__hip_atomic_fetch_add(&hist[pmc_pairobs_bin(r2, bscale, nbins)], 1u, __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                head = (head + 64) & RM;
+                C -= lim;
+            };
+            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+            auto block = [&](int jb, auto first_c) {
+                constexpr bool kFirst = decltype(first_c)::value;
+                const int j = jb + lane;
+                const bool vj = j < S;
+                const int jj = vj ? j : 0;
+                float xj = ox, yj = oy, zj = oz;
+                if constexpr (!kFirst) {
+                    xj = ex_[jj];
+                    yj = ey_[jj];
+                    zj = ez_[jj];
+                }
+                const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
+                for (int i = 0; i < n_own; ++i) {
+                    const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+                    const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+                    const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+                    const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
+                    unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rc2) & vm;
+                    if constexpr (kFirst) im &= ~(1ull << i);
+                    if (__builtin_amdgcn_inverse_ballot_w64(im)) ring[(head + C + mbcnt64(im)) & RM] = r2;
+                    const int k = __popcll(im);
+                    C += k;   // C < 64 + 64 <= ring size
+                    n_pairs += (unsigned long long)k;
+                    if (C >= 64) drain(64);
+                }
+            };
+            block(0, std::true_type{});
+            for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
+            if (C > 0) drain(C);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+        }
+    }
+    // ---- flush: wave sums (int64, exact in any order), this wave's nonzero bins
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kPairObsCopies - 1)) * (size_t)(kPairObsHead + nbins);
+    const unsigned long long head3 = lane == 0 ? (unsigned long long)sum : (lane == 1 ? n_pairs : n_part);
+    if (lane < kPairObsHead && head3 != 0) atomicAdd(&mine[lane], head3);
+    for (int b = lane; b < nbins; b += kWave) {
+        const unsigned h = hist[b];
+        if (h) atomicAdd(&mine[kPairObsHead + b], (unsigned long long)h);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // self-test of the deterministic math on the device (compared bitwise with the host oracle)
 // ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
@@ -2839,7 +3088,7 @@ static int64_t phase_cells(const DevGeom& g, int ncz) { return (int64_t)(g.cps_x
 
 // 32-bit byte offsets when the disk buffer (halo planes included) is below 4 GiB (every single-GPU
 // 256^3 config), else 64-bit addressing.  The env hooks on top of it are NOT symmetric: only
-// launch_subsweep reads PMC_FORCE_ADDR64, only the shift reads PMC_SHIFT_OFF32.
+// launch_subsweep and launch_pairobs read PMC_FORCE_ADDR64, only the shift reads PMC_SHIFT_OFF32.
 static bool disk_off32(const DevGeom& g) {
     const int64_t bytes = (int64_t)g.cps_x * g.cps_y * (g.nz_local + 2 * g.halo) * 3 * g.nmax * 4;
     return bytes < ((int64_t)1 << 32);
@@ -3246,6 +3495,27 @@ hipError_t launch_energy(const DevGeom& g, const float* disk, const int16_t* n,
     return hipGetLastError();
 }
 
+// acc: kPairObsCopies copies of [virial, pairs, particles, hist[nbins]], zeroed on st before the call.
+// A fixed grid: 4096 waves are 4 per SIMD of the chip, all resident at nmax <= 16 (7.9 KiB of LDS
+// per wave at 512 bins); fewer when the box has fewer runs.  A wave's LDS bin counters are u32: it
+// visits at most cells / 4096 + kPairObsRun cells of at most 27 * nmax^2 ordered pairs each, and
+// cells * 3 * nmax < 2^32 (pmc_create), so its counts stay below 2^32 * 9 * nmax / 4096 + 2^20 < 2^32.
+hipError_t launch_pairobs(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc,
+                          float rmax2, float bscale, int nbins, hipStream_t st) {
+    if (nbins < 1 || nbins > kPairObsMaxBins) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
+    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
+    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
+    const size_t lds = sizeof(float) * (3 * 27 * (size_t)g.nmax + kPairObsRing + 32 + (size_t)nbins);
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_subsweep
+    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
+        hipLaunchKernelGGL((k_pairobs<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, rmax2, bscale,
+                           nbins);
+    });
+    return hipGetLastError();
+}
 
 hipError_t launch_colour_rows(const DevGeom& g, const float* src, float* dst, int colour, int mode, hipStream_t st) {
     int o[3];

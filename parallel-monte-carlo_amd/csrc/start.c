@@ -4,12 +4,15 @@
  *
  *   start [--cps 4] [--atoms 64] [--passes 1000] [--nmax 16] [--moves 10] [--beta 0.3]
  *         [--sigma 0.5] [--w 2.5] [--seed 1234] [--every 1] [--graph]
- *         [--dump FILE] [--save FILE] [--restart FILE]
+ *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS]
  *
  * --dump writes create_dump frames (kernel.cu:510-536; the reference's VISUALISATION path) of the
  * initial state and after every --every sweeps; --save writes a PMCSNAP1 snapshot at the end;
  * --restart continues from a snapshot (its sweep index, state and statistics) instead of the
- * lattice, for --passes further sweeps.
+ * lattice, for --passes further sweeps.  --pairobs NBINS samples the pair observables of the final
+ * state (pmc_pair_observables, r_max = w): the g(r) table and one `pressure` line with the ideal part
+ * N/(V beta), the virial part W/(3V) and the impulsive part of the truncated, unshifted potential,
+ * (2 pi/3) rho^2 rc^3 g(rc) 4 (rc^-12 - rc^-6) with g(rc) from the last bin (negative).
  *
  * Prints "step: energy" lines like kernel.cu:643,695 (energy from the cell-list sum every
  * --every sweeps) and a final summary with acceptance ratio and trial-moves/s.  Compile-time
@@ -32,7 +35,7 @@ int main(int argc, char** argv) {
     p.cps_x = 4; p.nmax = 16; p.n_moves = 10;
     p.w = 2.5f; p.beta = 0.3f; p.sigma = 0.5f; p.seed = 1234;
     long long atoms = 64;
-    int passes = 1000, every = 1, graph = 0;
+    int passes = 1000, every = 1, graph = 0, pairobs = 0;
     const char *dump = NULL, *save = NULL, *restart = NULL;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -51,6 +54,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--dump")) { dump = v; ++i; }
         else if (!strcmp(a, "--save")) { save = v; ++i; }
         else if (!strcmp(a, "--restart")) { restart = v; ++i; }
+        else if (!strcmp(a, "--pairobs")) { pairobs = atoi(v); ++i; }
         else { fprintf(stderr, "unknown flag %s\n", a); return 2; }
     }
     if (every < 1) every = 1;
@@ -107,6 +111,34 @@ int main(int argc, char** argv) {
            (long long)total.trials, (long long)total.evaluated);
     if (seconds > 0)
         printf("# device time %.6f s, %.3e trial-moves/s\n", seconds, (double)total.trials / seconds);
+    if (pairobs) {
+        const double pi = 3.14159265358979323846;
+        uint64_t* hist = calloc(pairobs > 0 ? (size_t)pairobs : 1, sizeof(uint64_t));
+        pmc_pair_obs po;
+        pmc_params q;
+        if (!hist) die("calloc", 0);
+        if ((rc = pmc_get_params(ctx, &q))) die("pmc_get_params", rc);
+        if ((rc = pmc_pair_observables(ctx, q.w, pairobs, hist, &po))) die("pmc_pair_observables", rc);
+        const double rc_ = (double)q.w, n = (double)po.particles;
+        const double vol = (double)q.cps_x * (double)q.cps_y * (double)q.cps_z * rc_ * rc_ * rc_;
+        const double rho = n / vol, dr = rc_ / pairobs;
+        double g_last = 0.0;
+        printf("# g(r): bin centre, g, ordered pairs\n");
+        for (int b = 0; b < pairobs; ++b) {
+            const double r0 = b * dr, r1 = (b + 1) * dr;
+            const double shell = 4.0 / 3.0 * pi * (r1 * r1 * r1 - r0 * r0 * r0);
+            g_last = n > 0 ? (double)hist[b] / (n * rho * shell) : 0.0;
+            printf("g %.6f %.6f %llu\n", 0.5 * (r0 + r1), g_last, (unsigned long long)hist[b]);
+        }
+        const double w_vir = 12.0 * (double)po.virial_fixed / 4294967296.0;
+        const double i6 = 1.0 / (rc_ * rc_ * rc_ * rc_ * rc_ * rc_);
+        const double p_ideal = q.beta > 0.0f ? n / (vol * (double)q.beta) : 0.0;
+        const double p_vir = w_vir / (3.0 * vol);
+        const double p_imp = 2.0 * pi / 3.0 * rho * rho * rc_ * rc_ * rc_ * g_last * 4.0 * (i6 * i6 - i6);
+        printf("pressure %.9g ideal %.9g virial %.9g impulsive %.9g (N %lld, V %.6f, ordered pairs %lld)\n",
+               p_ideal + p_vir + p_imp, p_ideal, p_vir, p_imp, (long long)po.particles, vol, (long long)po.pairs);
+        free(hist);
+    }
     pmc_destroy(ctx);
     return 0;
 }

@@ -38,6 +38,12 @@ class Stats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class PairObs(C.Structure):
+    """``pmc_pair_obs``."""
+
+    _fields_ = [("virial_fixed", C.c_int64), ("pairs", C.c_int64), ("particles", C.c_int64)]
+
+
 class Result(C.Structure):
     """``pmc_result``."""
 
@@ -145,6 +151,7 @@ def lib():
         _sig(L, "pmc_sweep_plan_ex", i32, C.c_uint64, u32, C.c_float, u32, C.POINTER(C.c_int * 8),
              C.POINTER(C.c_int), C.POINTER(C.c_float))
         _sig(L, "pmc_energy", i32, _vp, C.POINTER(C.c_double))
+        _sig(L, "pmc_pair_observables", i32, _vp, C.c_float, i32, _vp, C.POINTER(PairObs))
         _sig(L, "pmc_stats_read", i32, _vp, C.POINTER(Stats), i32)
         _sig(L, "pmc_error_flags", i32, _vp, C.POINTER(C.c_uint32), i32)
         _sig(L, "pmc_copy_out", i32, _vp, _vp, _vp)

@@ -21,7 +21,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import PMC_IPC_HANDLE_BYTES, Params, Result, Stats, check, lib
+from ._lib import PMC_IPC_HANDLE_BYTES, PairObs, Params, Result, Stats, check, lib
 
 FIX_SCALE = 2.0 ** 32
 
@@ -290,6 +290,18 @@ class PmcContext:
         e = C.c_double()
         check("pmc_energy", lib().pmc_energy(self._h, C.byref(e)))
         return e.value
+
+    def pair_observables(self, r_max: Optional[float] = None, nbins: int = 64) -> dict:
+        """Virial sum and g(r) histogram of the owned cells' particles over ordered pairs
+        (pmc_pair_observables; r_max defaults to w).  Integer sums: a slab run's per-context results
+        add exactly.  pmc_amd.observables turns them into pressure and g(r)."""
+        hist = np.zeros(max(int(nbins), 0), np.uint64)
+        out = PairObs()
+        check("pmc_pair_observables",
+              lib().pmc_pair_observables(self._h, self.w if r_max is None else r_max, nbins,
+                                         hist.ctypes.data if hist.size else None, C.byref(out)))
+        return {"hist": hist, "virial_fixed": int(out.virial_fixed), "pairs": int(out.pairs),
+                "particles": int(out.particles)}
 
     def stats(self, reset: bool = False) -> dict:
         s = Stats()
