@@ -2082,40 +2082,46 @@ __global__ __launch_bounds__(kWave) void k_energy(DevGeom g, const float* __rest
             }
             S += __popcll(am);
         };
+        // slots [s0, s0 + HS), s0 = HS, 2*HS, ..., of the cells in mask mg that hold more than s0
+        // particles (k_pairobs' chunk loop; one chunk at NSLOT 16)
         auto overflow = [&](unsigned long long mg, bool filter) {
             if constexpr (HS < NSLOT) {
-                unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> (lane & 63)) & 1ull) && cur.cnt > HS);
-                while (ov) {
-                    int ks = 0, nc = 0;
-                    for (; nc < CPP && ov; ++nc) {
-                        const int kb = (int)__builtin_ctzll(ov);
-                        ov &= ov - 1ull;
-                        ks = ee == nc ? kb : ks;
+#pragma unroll 1
+                for (int s0 = HS; s0 < NSLOT; s0 += HS) {
+                    unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> (lane & 63)) & 1ull) && cur.cnt > s0);
+                    if (!ov) break;   // no cell of the group reaches this chunk: none reaches a later one
+                    while (ov) {
+                        int ks = 0, nc = 0;
+                        for (; nc < CPP && ov; ++nc) {
+                            const int kb = (int)__builtin_ctzll(ov);
+                            ov &= ov - 1ull;
+                            ks = ee == nc ? kb : ks;
+                        }
+                        const int c_cnt = __shfl(cur.cnt, ks);
+                        const int c_idx = __shfl(cur.kc, ks);
+                        const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
+                        const int ps = s0 + p;
+                        const bool act = ee < nc && ps < c_cnt;
+                        float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+                        if (act) {
+                            using DA = DiskAddr<OFF32>;
+                            const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
+                            DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+                            ux = ux + isx;
+                            uy = uy + isy;
+                            uz = uz + isz;
+                        }
+                        put(act && (!filter || near(ux, uy, uz)), ux, uy, uz);
                     }
-                    const int c_cnt = __shfl(cur.cnt, ks);
-                    const int c_idx = __shfl(cur.kc, ks);
-                    const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
-                    const int ps = HS + p;
-                    const bool act = ee < nc && ps < c_cnt;
-                    float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-                    if (act) {
-                        using DA = DiskAddr<OFF32>;
-                        const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
-                        DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
-                        ux = ux + isx;
-                        uy = uy + isy;
-                        uz = uz + isz;
-                    }
-                    put(act && (!filter || near(ux, uy, uz)), ux, uy, uz);
                 }
             }
         };
         const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell (entry 0)
         const int e0 = n0 + n1;
         // staged ranges: [0, n_own) own | main slots of the other cells in list order (weight-2
-        // cells first: [n_own, A)) | overflow slots of weight-2 cells [B, C) | of weight-1 cells
+        // cells first: [n_own, A)) | overflow slots of weight-2 cells [B, C2) | of weight-1 cells
         put(vact[0] && ee == 0, vx[0], vy[0], vz[0]);                 // own main slots
-        overflow(m0, false);                                          // own slots [HS, n)
+        overflow(m0, false);                                          // own slots [HS, n), every chunk
         int A = S;
 #pragma unroll
         for (int q = 0; q < NPMAX; ++q) {
