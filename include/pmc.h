@@ -136,7 +136,15 @@ int pmc_device_count(int* count);
 int pmc_init_r(pmc_ctx* ctx, int64_t n_atoms, float* d_r);
 /* assign (start.cu:87-146): bin d_r into d_disk/d_n with the reference's half-open rule
  * lb < x <= ub, particles of a cell in ascending index order.  Returns PMC_ERR_OVERFLOW if a
- * cell exceeds nmax, PMC_ERR_RANGE if a particle is outside the owned box. */
+ * cell exceeds nmax, PMC_ERR_RANGE if a particle is outside the owned box (-L/2 itself is outside,
+ * +L/2 inside; in a slab, another slab's planes are outside).  The buffers are written in both
+ * cases as the reference's sequential scan would leave them: a particle outside the owned box is
+ * skipped, a cell that more than nmax particles bin into keeps the FIRST nmax of them in index
+ * order (count nmax) and drops the rest, every other cell is unaffected; the result is the same from
+ * run to run.  (The over-full cells are refilled by an ordered rescan: an error path, not a fast
+ * one.)  When both errors occur the return value is PMC_ERR_RANGE; the C oracle's orc_assign
+ * returns whichever it met last.  The context's error flags are cleared first and then hold bit 1
+ * (overflow) and bit 2 (range) of this call. */
 int pmc_assign(pmc_ctx* ctx, const float* d_r, int64_t n_atoms, float* d_disk, int16_t* d_n);
 /* subsweep_kernel (subsweep.h:240-300): one checkerboard colour phase, offset = (ox,oy,oz)
  * in {0,1}^3 (start.cu:241-245).  `sweep` is the RNG counter (sweep index).  d_disk: the reference

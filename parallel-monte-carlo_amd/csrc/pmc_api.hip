@@ -507,12 +507,18 @@ int pmc_assign(pmc_ctx* c, const float* d_r, int64_t n_atoms, float* d_disk, int
         PMC_HIP(hipMalloc(&c->tmp_idx, sizeof(int32_t) * (size_t)c->cells * (size_t)c->P.nmax));
     }
     PMC_HIP(hipMemsetAsync(c->flags, 0, 16, c->stream));
+    const int ref_layout = is_state_buffer(c, d_disk) ? 0 : 1;
     hipError_t e = launch_assign(c->G, d_r, n_atoms, d_disk, d_n, c->tmp_cnt, c->tmp_idx, c->flags, c->stream, 0,
-                                 is_state_buffer(c, d_disk) ? 0 : 1);
+                                 ref_layout);
     if (e != hipSuccess) return hip_fail(e, "assign launch");
     uint32_t fl = 0;
     PMC_HIP(hipMemcpyAsync(&fl, c->flags, 4, hipMemcpyDeviceToHost, c->stream));
     PMC_HIP(hipStreamSynchronize(c->stream));
+    if (fl & 2u) {   // over-full cells keep their first nmax particles in index order (pmc.h)
+        e = launch_assign_refill(c->G, d_r, n_atoms, d_disk, c->tmp_cnt, c->stream, 0, ref_layout);
+        if (e != hipSuccess) return hip_fail(e, "assign refill launch");
+        PMC_HIP(hipStreamSynchronize(c->stream));
+    }
     if (fl & 4u) return fail(PMC_ERR_RANGE, "assign: particle outside the owned box");
     if (fl & 2u) return fail(PMC_ERR_OVERFLOW, "assign: cell occupancy exceeds nmax");
     return PMC_OK;
@@ -623,12 +629,18 @@ int pmc_init_lattice_planes(pmc_ctx* c, int64_t n_atoms_lattice, int32_t lattice
     PMC_HIP(hipMemsetAsync(c->flags, 0, 16, c->stream));
     // assign keeps the owned planes' particles (clip 1: other slabs' particles are skipped;
     // clip 2: also the lattice rows above the periodic box)
+    const int clip = lattice_cps_z > c->P.cps_z ? 2 : 1;
     e = launch_assign(c->G, c->d_r, n_atoms_lattice, c->disk[c->cur], c->n[c->cur], c->tmp_cnt, c->tmp_idx,
-                      c->flags, c->stream, lattice_cps_z > c->P.cps_z ? 2 : 1);
+                      c->flags, c->stream, clip);
     if (e != hipSuccess) return hip_fail(e, "assign launch");
     uint32_t fl = 0;
     PMC_HIP(hipMemcpyAsync(&fl, c->flags, 4, hipMemcpyDeviceToHost, c->stream));
     PMC_HIP(hipStreamSynchronize(c->stream));
+    if (fl & 2u) {   // as pmc_assign: the first nmax particles of an over-full cell in index order
+        e = launch_assign_refill(c->G, c->d_r, n_atoms_lattice, c->disk[c->cur], c->tmp_cnt, c->stream, clip, 0);
+        if (e != hipSuccess) return hip_fail(e, "assign refill launch");
+        PMC_HIP(hipStreamSynchronize(c->stream));
+    }
     if (fl & 4u) return fail(PMC_ERR_RANGE, "assign: particle outside the box");
     if (fl & 2u) return fail(PMC_ERR_OVERFLOW, "assign: cell occupancy exceeds nmax");
     return PMC_OK;

@@ -148,6 +148,10 @@ hipError_t launch_init_r(const DevGeom& g, int64_t n_atoms, int64_t n_cube, floa
 hipError_t launch_assign(const DevGeom& g, const float* r, int64_t n_atoms, float* disk, int16_t* n,
                          int32_t* tmp_cnt, int32_t* tmp_idx, uint32_t* flags, hipStream_t st, int clip = 0,
                          int ref_layout = 0);
+// the overflow path: after a launch_assign that raised flag bit 1 (same arguments, tmp_cnt untouched
+// since), the over-full cells rewritten with their first nmax particles in index order
+hipError_t launch_assign_refill(const DevGeom& g, const float* r, int64_t n_atoms, float* disk,
+                                const int32_t* tmp_cnt, hipStream_t st, int clip, int ref_layout);
 // segq: int[1 + energy_segments(g)] scratch, zeroed on st before the call
 size_t energy_segments(const DevGeom& g);
 hipError_t launch_energy(const DevGeom& g, const float* disk, const int16_t* n,

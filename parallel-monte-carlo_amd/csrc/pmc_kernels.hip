@@ -1751,29 +1751,75 @@ __device__ int bin_axis(float xv, int cps, float w) {
     return -1;
 }
 
+// storage cell of particle i, or -1 for a particle that is not binned: outside the box, or in another
+// slab's planes (*range: whether that is a range error under `clip`)
+__device__ __forceinline__ int64_t assign_cell(const DevGeom& g, const float* __restrict__ r, int64_t i,
+                                               int64_t n_atoms, int clip, bool* range) {
+    *range = false;
+    const int cx = bin_axis(r[i], g.cps_x, g.w);
+    const int cy = bin_axis(r[i + n_atoms], g.cps_y, g.w);
+    const float zv = r[i + 2 * n_atoms];
+    // clip 2 (pmc_init_lattice_planes): lattice rows above the periodic box are not part of it
+    if (clip == 2 && zv > g.Lz / 2.0f) return -1;
+    const int cz = bin_axis(zv, g.cps_z, g.w);
+    if (cx < 0 || cy < 0 || cz < 0) {
+        *range = true;
+        return -1;
+    }
+    if (cz < g.z0 || cz >= g.z0 + g.nz_local) {   // another slab's particle
+        *range = !clip;
+        return -1;
+    }
+    return sidx(g, cx, cy, cz - g.z0);
+}
+
 __global__ void k_assign_count(DevGeom g, const float* __restrict__ r, int64_t n_atoms,
                                int32_t* __restrict__ tmp_cnt, int32_t* __restrict__ tmp_idx,
                                uint32_t* __restrict__ flags, int clip) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_atoms) return;
-    const int cx = bin_axis(r[i], g.cps_x, g.w);
-    const int cy = bin_axis(r[i + n_atoms], g.cps_y, g.w);
-    const float zv = r[i + 2 * n_atoms];
-    // clip 2 (pmc_init_lattice_planes): lattice rows above the periodic box are not part of it
-    if (clip == 2 && zv > g.Lz / 2.0f) return;
-    const int cz = bin_axis(zv, g.cps_z, g.w);
-    if (cx < 0 || cy < 0 || cz < 0) {
-        atomicOr(flags, 4u);
+    bool range;
+    const int64_t c = assign_cell(g, r, i, n_atoms, clip, &range);
+    if (c < 0) {
+        if (range) atomicOr(flags, 4u);
         return;
     }
-    if (cz < g.z0 || cz >= g.z0 + g.nz_local) {   // another slab's particle
-        if (!clip) atomicOr(flags, 4u);
-        return;
-    }
-    const int64_t c = sidx(g, cx, cy, cz - g.z0);
     const int k = atomicAdd(&tmp_cnt[c], 1);
     if (k < g.nmax) tmp_idx[c * g.nmax + k] = (int32_t)i;
     else atomicOr(flags, 2u);
+}
+
+// The overflow path of assign (launched only after flag bit 1 was read back): k_assign_count kept
+// whichever nmax particles of an over-full cell won its atomicAdd.  One wave per cell rescans the
+// particles in index order, 64 at a time, and rewrites an over-full cell with the first nmax that
+// bin into it -- what the reference's sequential scan keeps, the same from run to run.  Slow (every
+// such wave reads particles until its cell is full), which an error path may be.
+__global__ __launch_bounds__(kWave) void k_assign_refill(DevGeom g, const float* __restrict__ r, int64_t n_atoms,
+                                                        const int32_t* __restrict__ tmp_cnt, float* __restrict__ disk,
+                                                        int64_t cells, int clip, int ref_layout) {
+    const int64_t c = (int64_t)blockIdx.x;
+    const int nm = g.nmax;
+    if (c >= cells || tmp_cnt[c] <= nm) return;
+    const int lane = threadIdx.x & (kWave - 1);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int64_t ds = ref_layout ? nm : (int64_t)lay_dim(nm), ss = ref_layout ? 1 : (int64_t)lay_slot();
+    int cnt = 0;
+    for (int64_t base = 0; base < n_atoms && cnt < nm; base += kWave) {
+        const int64_t i = base + lane;
+        bool mine = false;
+        if (i < n_atoms) {
+            bool range;
+            mine = assign_cell(g, r, i, n_atoms, clip, &range) == c;
+        }
+        const unsigned long long m = __ballot(mine);
+        const int k = cnt + __popcll(m & below);
+        if (mine && k < nm) {
+            disk[c * 3 * nm + k * ss] = r[i];
+            disk[c * 3 * nm + ds + k * ss] = r[i + n_atoms];
+            disk[c * 3 * nm + 2 * ds + k * ss] = r[i + 2 * n_atoms];
+        }
+        cnt += __popcll(m);
+    }
 }
 
 // per cell: order the slots by particle index (the reference scans particles in index order),
@@ -3441,6 +3487,16 @@ hipError_t launch_assign(const DevGeom& g, const float* r, int64_t n_atoms, floa
     dim3 grid2((unsigned)((cells + 255) / 256)), block2(256);
     hipLaunchKernelGGL(k_assign_fill, grid2, block2, 0, st, g, r, n_atoms, tmp_cnt, tmp_idx, disk, n, cells,
                        ref_layout);
+    return hipGetLastError();
+}
+
+// after a launch_assign whose flags showed bit 1 (tmp_cnt still holds its counts): rewrite the
+// over-full cells with their first nmax particles in index order
+hipError_t launch_assign_refill(const DevGeom& g, const float* r, int64_t n_atoms, float* disk,
+                                const int32_t* tmp_cnt, hipStream_t st, int clip, int ref_layout) {
+    const int64_t cells = (int64_t)g.cps_x * g.cps_y * (g.nz_local + 2 * g.halo);
+    hipLaunchKernelGGL(k_assign_refill, dim3((unsigned)cells), dim3(kWave), 0, st, g, r, n_atoms, tmp_cnt, disk, cells,
+                       clip, ref_layout);
     return hipGetLastError();
 }
 
