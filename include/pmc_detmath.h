@@ -233,10 +233,35 @@ PMC_HD int pmc_stage_split(int nmax) {
     return nslot >= 16 ? nslot / 2 : nslot;
 }
 
-/* own-cell closed box padded by PMC_BOX_PAD: lb = c*w - L/2.0f (start.cu:129), ub = lb + w */
+/* Lower bound of cell c along an axis of length L = (float)cps * w: lb(c) = c*w - L/2.0f
+ * (start.cu:129).  lb is non-decreasing in c (two monotone roundings) and lb(cps) = L - L/2 = L/2
+ * exactly, so the intervals (lb(c), lb(c+1)], c = 0..cps-1, tile (-L/2, L/2] for every w.  The
+ * reference's upper bound lb(c) + w (start.cu:130) does not: in float it can fall below lb(c+1)
+ * (w = 3.1f, cps = 8: lb(3) + w = -4.77e-7 < 0 = lb(4)) and leave a gap that belongs to no cell.
+ * For w = 2.5 and even cps both forms are exact and equal. */
+PMC_HD float pmc_cell_lb(int c, float w, float L) { return (float)c * w - L / 2.0f; }
+
+/* Cell of x along one axis by the tiling rule lb(c) < x <= lb(c+1); -1 outside (-L/2, L/2].
+ * assign (oracle and GPU) bins with this.  The first guess is off by at most one cell. */
+PMC_HD int pmc_bin_axis(float x, int cps, float w) {
+    const float L = (float)cps * w;
+    int c = (int)((x + L / 2.0f) / w);
+    if (c < 0) c = 0;
+    if (c > cps - 1) c = cps - 1;
+    for (int it = 0; it < 4; ++it) {
+        if (x <= pmc_cell_lb(c, w, L)) { if (c == 0) return -1; --c; }
+        else if (x > pmc_cell_lb(c + 1, w, L)) { if (c == cps - 1) return -1; ++c; }
+        else return c;
+    }
+    return -1;
+}
+
+/* own-cell closed box padded by PMC_BOX_PAD: lb = c*w - L/2.0f (start.cu:129), ub = lb + w.  The
+ * subsweep's out-of-bound test and shiftCells' keep rule may leave a particle a few ulp(L/2)
+ * outside its assign interval; the pad covers that ("Cell bounds"). */
 PMC_HD void pmc_cell_box(int cx, int cy, int cz, float w, float Lx, float Ly, float Lz, float lo[3],
                          float hi[3]) {
-    float lbx = (float)cx * w - Lx / 2.0f, lby = (float)cy * w - Ly / 2.0f, lbz = (float)cz * w - Lz / 2.0f;
+    float lbx = pmc_cell_lb(cx, w, Lx), lby = pmc_cell_lb(cy, w, Ly), lbz = pmc_cell_lb(cz, w, Lz);
     lo[0] = lbx - PMC_BOX_PAD; hi[0] = (lbx + w) + PMC_BOX_PAD;
     lo[1] = lby - PMC_BOX_PAD; hi[1] = (lby + w) + PMC_BOX_PAD;
     lo[2] = lbz - PMC_BOX_PAD; hi[2] = (lbz + w) + PMC_BOX_PAD;

@@ -121,22 +121,10 @@ int orc_init_r(const pmc_params* p, int64_t n_atoms, float* r) {
     return PMC_OK;
 }
 
-/* cell along one axis by the reference's half-open rule lb < x <= ub with
- * lb = c*w - L/2.0f (start.cu:129-134); -1 if outside (-L/2, L/2] */
-static int bin_axis(float x, int cps, float w) {
-    float L = (float)cps * w;
-    int c = (int)((x + L / 2.0f) / w);
-    if (c < 0) c = 0;
-    if (c > cps - 1) c = cps - 1;
-    for (int it = 0; it < 4; ++it) {
-        float lb = (float)c * w - L / 2.0f;
-        float ub = lb + w;
-        if (x <= lb) { if (c == 0) return -1; --c; }
-        else if (x > ub) { if (c == cps - 1) return -1; ++c; }
-        else return c;
-    }
-    return -1;
-}
+/* cell along one axis by the reference's half-open rule (start.cu:129-134) with the upper bound
+ * taken as the next cell's lower bound, lb(c) < x <= lb(c+1), so the cells tile (-L/2, L/2] for
+ * every w (pmc_bin_axis, pmc_detmath.h); -1 if outside */
+static int bin_axis(float x, int cps, float w) { return pmc_bin_axis(x, cps, w); }
 
 int orc_assign(const pmc_params* p, const float* r, int64_t n_atoms, float* disk, int16_t* n) {
     int64_t cells = orc_storage_cells(p);

@@ -1735,21 +1735,9 @@ __global__ void k_init_r(DevGeom g, int64_t n_atoms, int64_t nc, float* __restri
     r[idx + 2 * n_atoms] = (float)((double)zc + (double)Lzl / 2.0 * (1.0 - fz));
 }
 
-// half-open binning lb < x <= ub, lb = c*w - L/2.0f (start.cu:129-134); -1 if outside the box
-__device__ int bin_axis(float xv, int cps, float w) {
-    const float L = (float)cps * w;
-    int c = (int)((xv + L / 2.0f) / w);
-    if (c < 0) c = 0;
-    if (c > cps - 1) c = cps - 1;
-    for (int it = 0; it < 4; ++it) {
-        const float lb = (float)c * w - L / 2.0f;
-        const float ub = lb + w;
-        if (xv <= lb) { if (c == 0) return -1; --c; }
-        else if (xv > ub) { if (c == cps - 1) return -1; ++c; }
-        else return c;
-    }
-    return -1;
-}
+// half-open binning lb(c) < x <= lb(c+1), lb = c*w - L/2.0f (start.cu:129-134; the tiling rule of
+// pmc_bin_axis, shared with the oracle); -1 if outside the box
+__device__ int bin_axis(float xv, int cps, float w) { return pmc_bin_axis(xv, cps, w); }
 
 // storage cell of particle i, or -1 for a particle that is not binned: outside the box, or in another
 // slab's planes (*range: whether that is a range error under `clip`)

@@ -79,12 +79,12 @@ int main(int argc, char** argv) {
     double seconds = 0.0;
     for (int s0 = 0; s0 < passes; s0 += every) {
         int k = (passes - s0) < every ? (passes - s0) : every;
-        const int s = (int)first + s0;
+        const uint32_t s = first + (uint32_t)s0;   /* the sweep index wraps as the counter word does */
         pmc_result r;
         if (graph) {
             pmc_stats a, b;
             if ((rc = pmc_stats_read(ctx, &a, 0))) die("pmc_stats_read", rc);
-            if ((rc = pmc_run_graph(ctx, (uint32_t)s, k))) die("pmc_run_graph", rc);
+            if ((rc = pmc_run_graph(ctx, s, k))) die("pmc_run_graph", rc);
             if ((rc = pmc_synchronize(ctx))) die("pmc_synchronize", rc);
             if ((rc = pmc_stats_read(ctx, &b, 0))) die("pmc_stats_read", rc);
             if ((rc = pmc_energy(ctx, &e))) die("pmc_energy", rc);
@@ -94,7 +94,7 @@ int main(int argc, char** argv) {
             total.de_fixed += b.de_fixed - a.de_fixed;
         } else {
             /* energies once per interval (for the trace line), not around every pmc_start */
-            if ((rc = pmc_start_ex(ctx, (uint32_t)s, k, PMC_START_NO_ENERGY, &r))) die("pmc_start_ex", rc);
+            if ((rc = pmc_start_ex(ctx, s, k, PMC_START_NO_ENERGY, &r))) die("pmc_start_ex", rc);
             if ((rc = pmc_energy(ctx, &e))) die("pmc_energy", rc);
             seconds += r.seconds;
             total.accepted += r.stats.accepted;
@@ -102,8 +102,8 @@ int main(int argc, char** argv) {
             total.evaluated += r.stats.evaluated;
             total.de_fixed += r.stats.de_fixed;
         }
-        printf("%d: %f\n", s + k, e);
-        if (dump && (rc = pmc_dump_frame(ctx, dump, 1, (int64_t)(s + k)))) die("pmc_dump_frame", rc);
+        printf("%u: %f\n", (unsigned)(s + (uint32_t)k), e);
+        if (dump && (rc = pmc_dump_frame(ctx, dump, 1, (int64_t)(s + (uint32_t)k)))) die("pmc_dump_frame", rc);
     }
     if (save && (rc = pmc_save_snapshot(ctx, save, first + (uint32_t)passes))) die("pmc_save_snapshot", rc);
     printf("# acceptance %.6f (accepted %lld / trials %lld, energy-evaluated %lld)\n",

@@ -108,7 +108,7 @@ class SlabDriver:
                  atoms_total: int = 0, nmax: int = 16, n_moves: int = 10, seed: int = 1234,
                  use_rccl: Optional[bool] = None, group=None, local_group=None, cps_y: int = 0,
                  flags: int = 0, lattice_cps_z: int = 0, halo: int = 0, transport: Optional[str] = None,
-                 beta: float = 0.3):
+                 beta: float = 0.3, w: float = 2.5, sigma: float = 0.5):
         """local_group: a pmc_amd.engine.LocalGroup -- the in-process transport (this rank is one of
         local_group.world slab contexts of this process; construct and drive each rank from its
         own thread: the exchanges are collective).  flags: pmc_params.flags (PMC_FLAG_FULL_SHUFFLE:
@@ -121,7 +121,8 @@ class SlabDriver:
         several rank processes on ONE GPU, which RCCL refuses); "rccl"; "local" (world 1: periodic
         halos by local copies); "auto" -- IPC, or RCCL on every rank if any rank cannot map its peers.
         Default: PMC_SLAB_TRANSPORT, else "ipc" for world > 1, "local" for one rank (use_rccl=True:
-        "rccl", the one-rank RCCL rehearsal).  nmax, n_moves, beta, seed: pmc_params, as PmcContext."""
+        "rccl", the one-rank RCCL rehearsal).  nmax, n_moves, beta, seed, w, sigma: pmc_params, as
+        PmcContext."""
         from .engine import PmcContext, comm_unique_id
         self.g = SlabGeometry(cps, nz_local, rank, world, nmax)
         if stream is None and local_group is None:
@@ -134,7 +135,7 @@ class SlabDriver:
             halo = 1
         self.halo = halo
         self.ctx = PmcContext(cps, cps_y=cps_y, cps_z=self.g.cps_z, nz_local=nz_local, z0=self.g.z0, halo=halo,
-                              nmax=nmax, n_moves=n_moves, beta=beta, seed=seed, flags=flags,
+                              nmax=nmax, n_moves=n_moves, beta=beta, seed=seed, flags=flags, w=w, sigma=sigma,
                               stream=stream.cuda_stream if stream is not None else None)
         self.cps_y = cps_y or cps
         self._rank, self._world, self._group = rank, world, group
@@ -253,7 +254,7 @@ class SlabDriver:
 
     def run(self, first: int, count: int) -> None:
         for k in range(count):
-            self.sweep(first + k)
+            self.sweep((first + k) & 0xFFFFFFFF)   # the sweep index is a uint32 counter word
         self.finish()
 
     def load_state(self, disk, n) -> None:

@@ -122,12 +122,13 @@ def slab_of(name, nz_local, halo=1, z0=0):
 
 
 def brute_force_energy(kw, disk, n):
-    """Float64 sum over all pairs of the truncated Lennard-Jones energy: minimum image, r^2 <= rc^2,
-    r^2 clamped below at the oracle's r2min (orc_pair_energy's clamp)."""
+    """Float64 sum over all pairs of the truncated Lennard-Jones energy: minimum image in the box
+    L = cps * w (w = kw["w"], default 2.5), the reference's cutoff sqrtf(r^2) <= w on the float32
+    r^2 (subsweep.h:96-99), r^2 clamped below at the oracle's r2min (orc_pair_energy's clamp)."""
     cps, nmax = kw["cps"], kw["nmax"]
+    w = np.float32(kw.get("w", 2.5))
     pos = pmc_oracle.positions_from(disk, n, nmax).astype(np.float64)
-    box = cps * 2.5
-    rc2 = float(pmc_oracle.cutoff_r2(2.5))
+    box = float(np.float32(cps) * w)
     r2min = float(np.float32(R2_MIN))
     e = 0.0
     for i in range(0, len(pos), 512):        # pairs (i, j > i), 512 rows at a time
@@ -135,7 +136,8 @@ def brute_force_energy(kw, disk, n):
         d -= box * np.rint(d / box)
         r2 = (d * d).sum(axis=2)
         r2[np.tril_indices(len(r2), 0, r2.shape[1])] = np.inf       # j <= i
-        r2 = r2[r2 <= rc2]
+        r2 = r2[np.isfinite(r2)]
+        r2 = r2[np.sqrt(r2.astype(np.float32)) <= w]
         r2 = np.maximum(r2, r2min)
         p6 = 1.0 / (r2 * r2 * r2)
         e += float((4.0 * (p6 * p6 - p6)).sum())

@@ -155,19 +155,21 @@ def test_lattice_cube_root_exact(oracle):
 # ---------------------------------------------------------------------------------------------
 # algorithm invariants
 # ---------------------------------------------------------------------------------------------
-def _in_cells(st):
+def _in_cells(st, w=2.5):
+    """Every particle inside its cell's closed box [lb, lb + w], lb = c*w - L/2 in float32."""
     p = st.p
+    w = np.float32(w)
     d3 = st.disk3()
     cps = (p.cps_x, p.cps_y, p.cps_z)
     idx = np.arange(st.cells)
     coords = (idx % cps[0], (idx // cps[0]) % cps[1], idx // (cps[0] * cps[1]))
     mask = np.arange(st.nmax)[None, :] < st.n[:, None]
     for k in range(3):
-        L = cps[k] * 2.5
-        lb = (coords[k] * 2.5 - L / 2).astype(np.float32)[:, None]
+        L = np.float32(cps[k]) * w
+        lb = (coords[k].astype(np.float32) * w - L / np.float32(2.0))[:, None]
         v = d3[:, k, :]
         lbb = np.broadcast_to(lb, v.shape)
-        if not np.all((v[mask] >= lbb[mask]) & (v[mask] <= lbb[mask] + np.float32(2.5))):
+        if not np.all((v[mask] >= lbb[mask]) & (v[mask] <= lbb[mask] + w)):
             return False
     return True
 
