@@ -379,6 +379,24 @@ int pmc_plane_span(const pmc_ctx* ctx, int z_local, size_t* disk_off, size_t* di
  * h_out_d[2*count] = acceptance threshold + fixed-point energy.  Used by the parity tests to pin
  * host == device bit equality of every transcendental the kernels use. */
 int pmc_selftest_detmath(const uint32_t* h_words, int count, float* h_out_f, double* h_out_d);
+/* The subsweep kernel's scalar device functions, evaluated by the functions themselves over whole
+ * input domains (one launch; host arrays in and out):
+ *   PMC_SELFTEST_UDOMAIN  u = (2k+1) * 2^-24 for k = first .. first+count-1 (pmc_u01's values, k < 2^23):
+ *                         h_out_f[4*count] = pmc_logf(u), pmc_bm_radius(u), sin and cos of
+ *                         pmc_det_sincos_2pi(u);
+ *   PMC_SELFTEST_ACCEPT   the same k as the top 23 bits of an ACCEPT word, at inverse temperature
+ *                         `beta` (validated and turned into kernel arguments as for a real launch):
+ *                         h_out_f[2*count] = the threshold T = pmc_accept_threshold and the
+ *                         acceptance bound F the kernel compares dE/4 with (accept_bound);
+ *   PMC_SELFTEST_LJ       h_in[count] signed squared distances r2s (sign set: an old-position term):
+ *                         h_out_f[count] = the kernel's listed-term quarter energy (the r2 floor as
+ *                         one max instruction), h_out_i[count] = pmc_to_fixed_f32 of it.
+ * Arguments a kind does not use are ignored (may be NULL / 0). */
+#define PMC_SELFTEST_UDOMAIN 0
+#define PMC_SELFTEST_ACCEPT  1
+#define PMC_SELFTEST_LJ      2
+int pmc_selftest_scalar(int kind, uint32_t first, int64_t count, float beta, const float* h_in,
+                        float* h_out_f, int64_t* h_out_i);
 /* The HBM rate this GPU delivers (beside the 8 TB/s spec): best of `reps`
  * passes of a streaming read of `bytes` (16-B loads, nothing written) and of a copy of `bytes`
  * (read + write counted), GB/s; two buffers of `bytes` (>= 16 MiB) on the current device. */

@@ -155,7 +155,8 @@ int orc_assign(const pmc_params* p, const float* r, int64_t n_atoms, float* disk
 /* ------------------------------------------------------------------------------------- */
 static void subsweep_cell(const pmc_params* p, float* disk, const int16_t* n, int x, int y, int zl,
                           uint32_t sweep, float rc2, float* px_, float* py_, float* pz_,
-                          int64_t* de, int64_t* acc, int64_t* tri, int64_t* ev) {
+                          int64_t* de, int64_t* acc, int64_t* tri, int64_t* ev,
+                          orc_trace_rec* rec, int max_rec) {
     const int nm = p->nmax;
     const int64_t c = sidx(p, x, y, zl);
     const int n_own = n[c];
@@ -241,6 +242,8 @@ static void subsweep_cell(const pmc_params* p, float* disk, const int16_t* n, in
         ++*tri;
         float ddx = qx - cxf, ddy = qy - cyf, ddz = qz - czf;
         int out = (ddx > hw) || (ddx < -hw) || (ddy > hw) || (ddy < -hw) || (ddz > hw) || (ddz < -hw);
+        int nterms = 0, accepted = 0;
+        uint32_t de_bits = 0u;
         if (!out) {
             ++*ev;
             /* energies (calculate_old/new_energy, subsweep.h:175-191): dE = sum over partners
@@ -275,12 +278,19 @@ static void subsweep_cell(const pmc_params* p, float* disk, const int16_t* n, in
                 for (int l = 0; l < 64; ++l) lane[l] = t[l];
             }
             const float dE = lane[0];
+            nterms = t;
+            de_bits = pmc_fbits(dE);
             /* accept_move (subsweep.h:209-216) as beta*dE < -log(u) */
             if ((double)p->beta * (double)dE < (double)T) {
                 px_[i] = qx; py_[i] = qy; pz_[i] = qz;   /* :219-223 */
                 ++*acc;
                 de_cell = de_cell + (double)dE;
+                accepted = 1;
             }
+        }
+        if (rec && m < max_rec) {   /* orc_subsweep_trace: this cell's moves, nothing else changes */
+            rec[m].staged = K; rec[m].terms = nterms; rec[m].out = out; rec[m].accepted = accepted;
+            rec[m].de_bits = de_bits; rec[m].t_bits = pmc_fbits(T);
         }
         i += 1;
         if (i >= n_own) i = 0;
@@ -300,8 +310,9 @@ void orc_subsweep(const pmc_params* p, float* disk, const int16_t* n, int ox, in
 }
 
 /* the cells of the colour in local planes [zl_begin, zl_end) */
-void orc_subsweep_range(const pmc_params* p, float* disk, const int16_t* n, int ox, int oy, int oz,
-                        uint32_t sweep, int zl_begin, int zl_end, pmc_stats* st) {
+static void subsweep_range(const pmc_params* p, float* disk, const int16_t* n, int ox, int oy, int oz,
+                           uint32_t sweep, int zl_begin, int zl_end, pmc_stats* st, int tx, int ty, int tzl,
+                           orc_trace_rec* rec, int max_rec) {
     const float rc2 = pmc_cutoff_r2(p->w);
     const int ncx = p->cps_x / 2, ncy = p->cps_y / 2;
     int cz0 = zl_begin - oz <= 0 ? 0 : (zl_begin - oz + 1) / 2;
@@ -324,14 +335,34 @@ void orc_subsweep_range(const pmc_params* p, float* disk, const int16_t* n, int 
 #endif
         for (int64_t t = 0; t < total; ++t) {
             int a = (int)(t % ncx), b = (int)((t / ncx) % ncy), cz = (int)(t / ((int64_t)ncx * ncy));
-            subsweep_cell(p, disk, n, 2 * a + ox, 2 * b + oy, 2 * (cz0 + cz) + oz, sweep, rc2, xs, ys, zs,
-                          &de, &acc, &tri, &ev);
+            const int x = 2 * a + ox, y = 2 * b + oy, zl = 2 * (cz0 + cz) + oz;
+            const int traced = rec && x == tx && y == ty && zl == tzl;
+            subsweep_cell(p, disk, n, x, y, zl, sweep, rc2, xs, ys, zs, &de, &acc, &tri, &ev,
+                          traced ? rec : NULL, max_rec);
         }
         free(buf);
     }
     if (st) {
         st->de_fixed += de; st->accepted += acc; st->trials += tri; st->evaluated += ev;
     }
+}
+
+void orc_subsweep_range(const pmc_params* p, float* disk, const int16_t* n, int ox, int oy, int oz,
+                        uint32_t sweep, int zl_begin, int zl_end, pmc_stats* st) {
+    subsweep_range(p, disk, n, ox, oy, oz, sweep, zl_begin, zl_end, st, 0, 0, 0, NULL, 0);
+}
+
+/* orc_subsweep that also records the moves of cell (x, y, zl): the same subsweep_cell, which fills
+ * records[m] for move m < max_records.  Returns the number of records written (0 when the cell is
+ * empty or not of this colour). */
+int orc_subsweep_trace(const pmc_params* p, float* disk, const int16_t* n, int ox, int oy, int oz,
+                       uint32_t sweep, int x, int y, int zl, orc_trace_rec* records, int max_records,
+                       pmc_stats* st) {
+    if (!records || max_records < 0) return PMC_ERR_ARG;
+    if (x < 0 || y < 0 || zl < 0 || x >= p->cps_x || y >= p->cps_y || zl >= p->nz_local) return PMC_ERR_ARG;
+    const int hit = (x & 1) == ox && (y & 1) == oy && (zl & 1) == oz && n[sidx(p, x, y, zl)] > 0;
+    subsweep_range(p, disk, n, ox, oy, oz, sweep, 0, p->nz_local, st, x, y, zl, records, max_records);
+    return hit ? (p->n_moves < max_records ? p->n_moves : max_records) : 0;
 }
 
 /* ------------------------------------------------------------------------------------- */
@@ -420,7 +451,10 @@ double orc_energy(const pmc_params* p, const float* disk, const int16_t* n) {
     int off[27][3];
     stencil_offsets(off);
     const int64_t total = (int64_t)p->cps_x * p->cps_y * p->nz_local;
-    int64_t sum = 0;
+    /* unsigned: the directed fixed-point sum wraps modulo 2^64 like the device's 64-bit atomics (and the
+     * virial sum, include/pmc_pairobs.h).  It is an energy only while it stays inside the int64 range:
+     * one overlapping pair (two directed terms clamped to 2^62) already leaves it */
+    uint64_t sum = 0;
 #ifdef _OPENMP
 #pragma omp parallel for num_threads(g_threads > 0 ? g_threads : 1) if (g_threads > 0) \
     reduction(+ : sum) schedule(static)
@@ -438,12 +472,12 @@ double orc_energy(const pmc_params* p, const float* disk, const int16_t* n) {
                     float xj = disk[b.idx * 3 * nm + q] + b.sx;
                     float yj = disk[b.idx * 3 * nm + nm + q] + b.sy;
                     float zj = disk[b.idx * 3 * nm + 2 * nm + q] + b.sz;
-                    sum += pmc_to_fixed((double)pmc_lj_from_r2(pmc_r2(xi - xj, yi - yj, zi - zj), rc2));
+                    sum += (uint64_t)pmc_to_fixed((double)pmc_lj_from_r2(pmc_r2(xi - xj, yi - yj, zi - zj), rc2));
                 }
             }
         }
     }
-    return (double)sum / PMC_FIX_SCALE * 0.5;
+    return (double)(int64_t)sum / PMC_FIX_SCALE * 0.5;
 }
 
 /* ------------------------------------------------------------------------------------- */
@@ -514,3 +548,26 @@ void orc_sweep_plan_ex(uint64_t seed, uint32_t sweep, float w, uint32_t flags, i
 }
 int64_t orc_to_fixed(double e) { return pmc_to_fixed(e); }
 int64_t orc_to_fixed_f32(float f) { return pmc_to_fixed_f32(f); }
+
+/* batch forms over whole input domains (one call per array: the exhaustive scalar tests) */
+void orc_udomain_batch(uint32_t first, int64_t count, float* out) {
+    for (int64_t i = 0; i < count; ++i) {
+        const float u = pmc_u01((first + (uint32_t)i) << 9);
+        out[4 * i + 0] = pmc_logf(u);
+        out[4 * i + 1] = pmc_bm_radius(u);
+        pmc_det_sincos_2pi(u, &out[4 * i + 2], &out[4 * i + 3]);
+    }
+}
+void orc_accept_threshold_batch(uint32_t first, int64_t count, float* out) {
+    for (int64_t i = 0; i < count; ++i) {
+        pmc_u32x4 w;
+        w.v[0] = (first + (uint32_t)i) << 9; w.v[1] = 0u; w.v[2] = 0u; w.v[3] = 0u;
+        out[i] = pmc_accept_threshold(w);
+    }
+}
+void orc_lj4_signed_batch(const float* r2s, int64_t count, float* out_f, int64_t* out_i) {
+    for (int64_t i = 0; i < count; ++i) {
+        out_f[i] = pmc_lj4_signed(r2s[i]);
+        out_i[i] = pmc_to_fixed_f32(out_f[i]);
+    }
+}

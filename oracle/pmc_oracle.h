@@ -40,6 +40,20 @@ void orc_subsweep(const pmc_params* p, float* disk, const int16_t* n, int ox, in
                   uint32_t sweep, pmc_stats* st);
 void orc_subsweep_range(const pmc_params* p, float* disk, const int16_t* n, int ox, int oy, int oz,
                         uint32_t sweep, int zl_begin, int zl_end, pmc_stats* st);
+/* orc_subsweep recording, for the one cell (x, y, zl), every move's decisions (the same code path:
+ * the record is filled inside the cell visit).  records[m], m < min(n_moves, max_records); returns
+ * the number written, 0 if the cell is empty or not of the colour, PMC_ERR_ARG on bad arguments. */
+typedef struct {
+    int32_t staged;     /* K: partners staged for the visit (own cell + filtered neighbours) */
+    int32_t terms;      /* listed pair terms of the move (new + old within the cutoff); 0 if out */
+    int32_t out;        /* the trial position left the cell */
+    int32_t accepted;
+    uint32_t de_bits;   /* float bits of the move's dE; 0 if out */
+    uint32_t t_bits;    /* float bits of the acceptance threshold T */
+} orc_trace_rec;
+int orc_subsweep_trace(const pmc_params* p, float* disk, const int16_t* n, int ox, int oy, int oz,
+                       uint32_t sweep, int x, int y, int zl, orc_trace_rec* records, int max_records,
+                       pmc_stats* st);
 /* shiftCells (CUDA-Parallel-MC/CUDA-Parallel-MC/shiftCells.h:23-112) -- returns overflow count */
 int orc_shift_cells(const pmc_params* p, const float* din, const int16_t* nin, float* dout,
                     int16_t* nout, int f, float d);
@@ -69,6 +83,10 @@ void orc_sweep_plan(uint64_t seed, uint32_t sweep, float w, int order[8], int* f
 void orc_sweep_plan_ex(uint64_t seed, uint32_t sweep, float w, uint32_t flags, int order[8], int* f, float* d);
 int64_t orc_to_fixed(double e);
 int64_t orc_to_fixed_f32(float f);
+/* batch forms: k = first .. first+count-1 is pmc_u01's k, u = (2k+1) * 2^-24 */
+void orc_udomain_batch(uint32_t first, int64_t count, float* out);          /* out[4*count]: logf, bm_radius, sin, cos */
+void orc_accept_threshold_batch(uint32_t first, int64_t count, float* out); /* out[count]: T of word k << 9 */
+void orc_lj4_signed_batch(const float* r2s, int64_t count, float* out_f, int64_t* out_i);
 
 #ifdef __cplusplus
 }

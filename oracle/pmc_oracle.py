@@ -68,6 +68,9 @@ _lib = None
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _i16p = np.ctypeslib.ndpointer(np.int16, flags="C_CONTIGUOUS")
+# orc_trace_rec (pmc_oracle.h): one record per move of the traced cell
+TRACE_DTYPE = np.dtype([("staged", np.int32), ("terms", np.int32), ("out", np.int32), ("accepted", np.int32),
+                        ("de_bits", np.uint32), ("t_bits", np.uint32)])
 
 
 def lib():
@@ -120,6 +123,16 @@ def lib():
         L.orc_to_fixed.restype = C.c_int64
         L.orc_to_fixed_f32.argtypes = [C.c_float]
         L.orc_to_fixed_f32.restype = C.c_int64
+        L.orc_subsweep_trace.argtypes = [P, _f32p, _i16p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int,
+                                         C.c_int, np.ctypeslib.ndpointer(TRACE_DTYPE, flags="C_CONTIGUOUS"),
+                                         C.c_int, C.POINTER(Stats)]
+        L.orc_udomain_batch.argtypes = [C.c_uint32, C.c_int64, _f32p]
+        L.orc_udomain_batch.restype = None
+        L.orc_accept_threshold_batch.argtypes = [C.c_uint32, C.c_int64, _f32p]
+        L.orc_accept_threshold_batch.restype = None
+        L.orc_lj4_signed_batch.argtypes = [_f32p, C.c_int64, _f32p,
+                                           np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")]
+        L.orc_lj4_signed_batch.restype = None
         _lib = L
     return _lib
 
@@ -158,6 +171,18 @@ class OracleState:
     def subsweep(self, offset, sweep: int):
         lib().orc_subsweep(C.byref(self.p), self.disk, self.n, int(offset[0]), int(offset[1]),
                            int(offset[2]), sweep, C.byref(self.stats))
+
+    def subsweep_trace(self, offset, sweep: int, cell, max_records: int | None = None) -> np.ndarray:
+        """subsweep(offset, sweep) that also returns the per-move records (TRACE_DTYPE) of the cell
+        (x, y, zl) -- the same cell visit code, see orc_subsweep_trace."""
+        m = self.p.n_moves if max_records is None else max_records
+        rec = np.zeros(m, TRACE_DTYPE)
+        got = lib().orc_subsweep_trace(C.byref(self.p), self.disk, self.n, int(offset[0]), int(offset[1]),
+                                       int(offset[2]), sweep, int(cell[0]), int(cell[1]), int(cell[2]), rec, m,
+                                       C.byref(self.stats))
+        if got < 0:
+            raise ValueError(f"orc_subsweep_trace: rc={got}")
+        return rec[:got]
 
     def shift_cells(self, f: int, d: float) -> int:
         dout = self.disk.copy()
@@ -243,6 +268,34 @@ def det_sincos_2pi(u: float):
     s, c = C.c_float(), C.c_float()
     lib().orc_det_sincos_2pi(u, C.byref(s), C.byref(c))
     return s.value, c.value
+
+
+def move_normals(words):
+    w = (C.c_uint32 * 4)(*[int(v) for v in words])
+    g = (C.c_float * 3)()
+    lib().orc_move_normals(C.byref(w), C.byref(g))
+    return np.array(list(g), np.float32)
+
+
+def udomain_batch(first: int = 0, count: int = 1 << 23) -> np.ndarray:
+    """float32 (count, 4): pmc_logf, pmc_bm_radius, sin, cos of pmc_det_sincos_2pi at u_k = (2k+1)/2^24."""
+    out = np.empty(4 * count, np.float32)
+    lib().orc_udomain_batch(first, count, out)
+    return out.reshape(count, 4)
+
+
+def accept_threshold_batch(first: int = 0, count: int = 1 << 23) -> np.ndarray:
+    out = np.empty(count, np.float32)
+    lib().orc_accept_threshold_batch(first, count, out)
+    return out
+
+
+def lj4_signed_batch(r2s):
+    r2s = np.ascontiguousarray(r2s, np.float32).ravel()
+    out_f = np.empty(r2s.size, np.float32)
+    out_i = np.empty(r2s.size, np.int64)
+    lib().orc_lj4_signed_batch(r2s, r2s.size, out_f, out_i)
+    return out_f, out_i
 
 
 def sweep_plan(seed: int, sweep: int, w: float = 2.5, flags: int = 0):

@@ -1007,6 +1007,42 @@ int pmc_selftest_detmath(const uint32_t* h_words, int count, float* h_out_f, dou
     return e == hipSuccess ? PMC_OK : hip_fail(e, "selftest");
 }
 
+int pmc_selftest_scalar(int kind, uint32_t first, int64_t count, float beta, const float* h_in, float* h_out_f,
+                        int64_t* h_out_i) {
+    const bool lj = kind == PMC_SELFTEST_LJ;
+    if (kind != PMC_SELFTEST_UDOMAIN && kind != PMC_SELFTEST_ACCEPT && !lj) return fail(PMC_ERR_ARG, "unknown kind");
+    if (!h_out_f || count < 0 || count > ((int64_t)1 << 23)) return fail(PMC_ERR_ARG, "bad argument");
+    if (lj ? (!h_in || !h_out_i) : (int64_t)first + count > ((int64_t)1 << 23))
+        return fail(PMC_ERR_ARG, lj ? "bad argument" : "k runs over the 2^23 values of pmc_u01");
+    // beta reaches the kernel the way a context's does: normalise() validates it, make_geom()
+    // derives the kernel arguments (beta, inv_b4, r2min)
+    pmc_params p = {};
+    p.cps_x = 4; p.nmax = 16; p.w = 2.5f; p.sigma = 0.5f;
+    p.beta = kind == PMC_SELFTEST_ACCEPT ? beta : 1.0f;
+    const int rc = normalise(&p);
+    if (rc != PMC_OK) return rc;
+    const HostGeom g = make_geom(p);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PMC_ERR_NODEV, "no HIP device");
+    if (count == 0) return PMC_OK;
+    const size_t per = kind == PMC_SELFTEST_UDOMAIN ? 4 : (kind == PMC_SELFTEST_ACCEPT ? 2 : 1);
+    const size_t fbytes = sizeof(float) * per * (size_t)count, ibytes = sizeof(int64_t) * (size_t)count;
+    float *din = nullptr, *df = nullptr;
+    int64_t* di = nullptr;
+    hipError_t e = hipMalloc(&df, fbytes);
+    if (e == hipSuccess && lj) e = hipMalloc(&din, sizeof(float) * (size_t)count);
+    if (e == hipSuccess && lj) e = hipMalloc(&di, ibytes);
+    if (e == hipSuccess && lj) e = hipMemcpy(din, h_in, sizeof(float) * (size_t)count, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_selftest_scalar(g, kind, first, count, din, df, di, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(h_out_f, df, fbytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && lj) e = hipMemcpy(h_out_i, di, ibytes, hipMemcpyDeviceToHost);
+    if (din) (void)hipFree(din);
+    if (df) (void)hipFree(df);
+    if (di) (void)hipFree(di);
+    return e == hipSuccess ? PMC_OK : hip_fail(e, "selftest_scalar");
+}
+
 int pmc_hbm_probe(uint64_t bytes, int reps, double* read_gbs, double* copy_gbs) {
     if (!read_gbs || !copy_gbs || reps < 1 || bytes < ((uint64_t)1 << 24)) return fail(PMC_ERR_ARG, "bad argument");
     int ndev = 0;

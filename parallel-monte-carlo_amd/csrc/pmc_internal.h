@@ -202,5 +202,8 @@ hipError_t launch_xfer(const XferCopy& cp, const XferFlags& w, uint64_t* ready, 
                        unsigned* done, uint64_t timeout_ticks, uint32_t* err, hipStream_t st);
 hipError_t launch_selftest(const uint32_t* words, int count, float* out_f, double* out_d,
                            float rc2, hipStream_t st);
+// pmc_selftest_scalar: count <= 2^23 inputs, one thread each; in / out_i only for PMC_SELFTEST_LJ
+hipError_t launch_selftest_scalar(const DevGeom& g, int kind, uint32_t first, int64_t count, const float* in,
+                                  float* out_f, int64_t* out_i, hipStream_t st);
 
 }  // namespace pmc

@@ -2788,6 +2788,35 @@ __global__ void k_selftest(const uint32_t* __restrict__ words, int count, float*
     out_d[2 * i + 1] = (double)pmc_to_fixed((double)out_f[4 * i + 3]);
 }
 
+// pmc_selftest_scalar: the subsweep's scalar device functions (the ones the moves call, no copies)
+// over a whole input domain, one thread per input.  kind: PMC_SELFTEST_* (include/pmc.h).
+__global__ __launch_bounds__(256) void k_selftest_scalar(DevGeom g, int kind, uint32_t first, int64_t count,
+                                                         const float* __restrict__ in, float* __restrict__ out_f,
+                                                         long long* __restrict__ out_i) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t word = (first + (uint32_t)i) << 9;   // pmc_u01 reads the top 23 bits
+    if (kind == PMC_SELFTEST_UDOMAIN) {
+        const float u = pmc_u01(word);
+        float s, c;
+        pmc_det_sincos_2pi(u, &s, &c);
+        out_f[4 * i + 0] = pmc_logf(u);
+        out_f[4 * i + 1] = pmc_bm_radius(u);
+        out_f[4 * i + 2] = s;
+        out_f[4 * i + 3] = c;
+    } else if (kind == PMC_SELFTEST_ACCEPT) {
+        pmc_u32x4 w;
+        w.v[0] = word; w.v[1] = 0u; w.v[2] = 0u; w.v[3] = 0u;
+        const float T = pmc_accept_threshold(w);
+        out_f[2 * i + 0] = T;
+        out_f[2 * i + 1] = accept_bound(T, g);
+    } else {
+        const float u4 = lj4_signed_max(in[i], g.r2min);
+        out_f[i] = u4;
+        out_i[i] = (long long)pmc_to_fixed_f32(u4);
+    }
+}
+
 // Reference layout <-> state layout (pmc_internal.h, PMC_AOS): element e of cell c, e = d*nmax + s in
 // the reference, d + 3*s in the packed layout.  One thread per float, coalesced on the destination.
 __global__ void k_relayout(const float* __restrict__ src, float* __restrict__ dst, int64_t total, int nm,
@@ -3581,6 +3610,14 @@ hipError_t launch_selftest(const uint32_t* words, int count, float* out_f, doubl
                            hipStream_t st) {
     dim3 grid((unsigned)((count + 255) / 256)), block(256);
     hipLaunchKernelGGL(k_selftest, grid, block, 0, st, words, count, out_f, out_d, rc2);
+    return hipGetLastError();
+}
+
+hipError_t launch_selftest_scalar(const DevGeom& g, int kind, uint32_t first, int64_t count, const float* in,
+                                  float* out_f, int64_t* out_i, hipStream_t st) {
+    dim3 grid((unsigned)((count + 255) / 256)), block(256);
+    hipLaunchKernelGGL(k_selftest_scalar, grid, block, 0, st, g, kind, first, count, in, out_f,
+                       reinterpret_cast<long long*>(out_i));
     return hipGetLastError();
 }
 

@@ -400,6 +400,27 @@ def selftest_detmath(words: np.ndarray):
     return out_f.reshape(cnt, 4), out_d.reshape(cnt, 2)
 
 
+SELFTEST_UDOMAIN, SELFTEST_ACCEPT, SELFTEST_LJ = 0, 1, 2     # PMC_SELFTEST_* (include/pmc.h)
+
+
+def selftest_scalar(kind: int, first: int = 0, count: int = 1 << 23, beta: float = 1.0, r2s=None):
+    """The subsweep's scalar device functions over a whole domain (pmc_selftest_scalar, diagnostic).
+    u-domain: float32 (count, 4) = logf, Box-Muller radius, sin, cos of u_k = (2k+1)/2^24, k from
+    `first`; accept: float32 (count, 2) = threshold T and acceptance bound F at `beta`; lj: for the
+    signed squared distances `r2s`, (float32 quarter energies, int64 fixed-point values)."""
+    if kind == SELFTEST_LJ:
+        r2s = np.ascontiguousarray(r2s, np.float32).ravel()
+        out_f = np.empty(r2s.size, np.float32)
+        out_i = np.empty(r2s.size, np.int64)
+        check("pmc_selftest_scalar", lib().pmc_selftest_scalar(kind, 0, r2s.size, 0.0, r2s.ctypes.data,
+                                                               out_f.ctypes.data, out_i.ctypes.data))
+        return out_f, out_i
+    per = 4 if kind == SELFTEST_UDOMAIN else 2
+    out_f = np.empty((count, per), np.float32)
+    check("pmc_selftest_scalar", lib().pmc_selftest_scalar(kind, first, count, beta, None, out_f.ctypes.data, None))
+    return out_f
+
+
 def hbm_probe(nbytes: int = 1 << 30, reps: int = 10) -> tuple:
     """(read GB/s, copy GB/s): the library's streaming read and copy kernels over `nbytes`, best of
     `reps` (pmc_hbm_probe; SURVEY.md Appendix D's achievable peak beside the 8 TB/s spec)."""
