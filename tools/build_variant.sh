@@ -8,4 +8,4 @@ OUT=$D/build/variants
 mkdir -p $OUT
 F="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -I$D/csrc"
 /opt/rocm/bin/hipcc $F -mllvm -amdgpu-atomic-optimizer-strategy=None "$@" -c -o $OUT/k_$NAME.o $SRC
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/lib_$NAME.so $OUT/k_$NAME.o $D/build/pmc_api.o $D/build/pmc_io.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/lib_$NAME.so $OUT/k_$NAME.o $D/build/pmc_api.o $D/build/pmc_slab.o $D/build/pmc_io.o
