@@ -354,6 +354,31 @@ typedef struct pmc_pair_obs {
     int64_t particles;     /* particles in owned cells */
 } pmc_pair_obs;
 int pmc_pair_observables(pmc_ctx* ctx, float r_max, int nbins, uint64_t* h_hist, pmc_pair_obs* out);
+/* Test-particle energies, defined bit for bit in pmc_probe.h: the energy dU of a probe with the
+ * particles of its cell's 27-cell stencil, sorted into an integer histogram that carries per-bin
+ * energy sums.  mode PMC_PROBE_INSERT (0): k_per_cell (1..64) uniform Widom insertions per owned
+ * cell, drawn from (seed, cell, `sample`); the excess chemical potential follows on the host from
+ * <exp(-beta dU)> (pmc_amd.observables.mu_excess).  mode PMC_PROBE_REAL (1): every owned particle
+ * probed at its own position with itself skipped (k_per_cell and sample ignored): with the insert
+ * distribution the overlapping-distribution check of that estimate.  The kernel takes no beta.
+ * h_hist / h_esum are HOST pointers to nbins entries: bin b counts the probes with
+ * e_lo + b * width <= dU < e_lo + (b + 1) * width (in the header's fixed-point units) and sums their
+ * quarter energies E4 (dU = 4 * E4 / 2^32); probes outside go to below / above, probes with a partner
+ * closer than 0.5 to overlaps.  PMC_ERR_ARG for a null pointer, an unknown mode, k_per_cell outside
+ * 1..64 (insert mode), nbins outside 1..512, a range that is not e_lo < e_hi with both of magnitude
+ * <= 2^20 and a bin width of at least one unit, and for a slab context with a pending deferred z
+ * exchange (pmc_slab_finish first).  Runs on the context stream and synchronises; state, statistics
+ * and error flags are left unchanged.  No cross-rank reduction: every output is an integer sum, the
+ * per-context results of a slab run add exactly (the insert draws use the global cell id). */
+typedef struct pmc_probe_obs {
+    int64_t probes;    /* probes evaluated: k_per_cell * owned cells, or owned particles */
+    int64_t overlaps;  /* hard probes (a partner at r2 < 0.25): exp(-beta dU) = 0, not binned */
+    int64_t below;     /* dU below the range */
+    int64_t above;     /* dU above the range */
+    int64_t pairs;     /* (probe, partner) pairs with r2 <= rc2 */
+} pmc_probe_obs;
+int pmc_probe_energies(pmc_ctx* ctx, int mode, int k_per_cell, uint32_t sample, float e_lo, float e_hi, int nbins,
+                       uint64_t* h_hist, int64_t* h_esum, pmc_probe_obs* out);
 /* Read and optionally reset the accumulated subsweep statistics (synchronises). */
 int pmc_stats_read(pmc_ctx* ctx, pmc_stats* out, int reset);
 /* Device error flags (bit 0: shift overflow, bit 1: assign overflow, bit 2: assign range, bits 3-4:

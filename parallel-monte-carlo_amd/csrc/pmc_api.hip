@@ -13,11 +13,13 @@
 
 #include "pmc_ctx.h"
 #include "../../include/pmc_pairobs.h"
+#include "../../include/pmc_probe.h"
 
 using namespace pmc;
 using namespace pmc_sched;
 
 static_assert(kPairObsMaxBins == PMC_PAIROBS_MAX_BINS, "pair observables: bin cap");
+static_assert(kProbeMaxBins == PMC_PROBE_MAX_BINS, "test-particle energies: bin cap");
 
 int pmc::issue_phases(pmc_ctx* c, hipStream_t st, int* ovf, unsigned long long* stats, int z0, int z1, uint32_t sweep,
                       const pmc_sweep_plan_t& plan, int k0, int k1, PhaseKind kind, float* mirror, int64_t phase0) {
@@ -301,6 +303,7 @@ void pmc_destroy(pmc_ctx* c) {
     if (c->eacc) (void)hipFree(c->eacc);
     if (c->segq) (void)hipFree(c->segq);
     if (c->pobs) (void)hipFree(c->pobs);
+    if (c->probe_acc) (void)hipFree(c->probe_acc);
     if (c->flags) (void)hipFree(c->flags);
     if (c->ovf) (void)hipFree(c->ovf);
     if (c->ovf_aux) (void)hipFree(c->ovf_aux);
@@ -691,6 +694,48 @@ int pmc_pair_observables(pmc_ctx* c, float r_max, int nbins, uint64_t* h_hist, p
     out->pairs = (int64_t)s[1];
     out->particles = (int64_t)s[2];
     for (int b = 0; b < nbins; ++b) h_hist[b] = (uint64_t)s[(size_t)kPairObsHead + (size_t)b];
+    return PMC_OK;
+}
+
+int pmc_probe_energies(pmc_ctx* c, int mode, int k_per_cell, uint32_t sample, float e_lo, float e_hi, int nbins,
+                       uint64_t* h_hist, int64_t* h_esum, pmc_probe_obs* out) {
+    if (!c || !h_hist || !h_esum || !out) return fail(PMC_ERR_ARG, "bad argument");
+    if (mode != PMC_PROBE_INSERT && mode != PMC_PROBE_REAL)
+        return fail(PMC_ERR_ARG, "pmc_probe_energies: mode must be PMC_PROBE_INSERT or PMC_PROBE_REAL");
+    if (mode == PMC_PROBE_INSERT && (k_per_cell < 1 || k_per_cell > PMC_PROBE_MAX_K))
+        return fail(PMC_ERR_ARG, "pmc_probe_energies: k_per_cell must be in 1..64");
+    if (nbins < 1 || nbins > PMC_PROBE_MAX_BINS) return fail(PMC_ERR_ARG, "pmc_probe_energies: nbins must be in 1..512");
+    int64_t lo4 = 0, bw4 = 0;
+    if (pmc_probe_range(e_lo, e_hi, nbins, &lo4, &bw4))
+        return fail(PMC_ERR_ARG, "pmc_probe_energies: the range must be e_lo < e_hi, both of magnitude <= 2^20, with a "
+                                 "bin width of at least 2^-32");
+    // the kernel reads both halos, as the energy does (energy_fixed)
+    if (slab_pending_zdir(c))
+        return fail(PMC_ERR_ARG, "pmc_probe_energies: a slab halo exchange is pending (call pmc_slab_finish first)");
+    if (int rj = slab_join(c)) return rj;
+    const size_t per = (size_t)kProbeHead + 2 * (size_t)nbins;
+    if (!c->probe_acc)
+        PMC_HIP(hipMalloc(&c->probe_acc, sizeof(unsigned long long) * kProbeCopies * (kProbeHead + 2 * kProbeMaxBins)));
+    PMC_HIP(hipMemsetAsync(c->probe_acc, 0, sizeof(unsigned long long) * kProbeCopies * per, c->stream));
+    hipError_t e = launch_probe(c->G, c->disk[c->cur], c->n[c->cur], c->probe_acc, mode, k_per_cell, sample, lo4, bw4,
+                                nbins, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "test-particle energies launch");
+    std::vector<unsigned long long> h((size_t)kProbeCopies * per);
+    PMC_HIP(hipMemcpyAsync(h.data(), c->probe_acc, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost,
+                           c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    std::vector<unsigned long long> s(per, 0ull);
+    for (int k = 0; k < kProbeCopies; ++k)
+        for (size_t i = 0; i < per; ++i) s[i] += h[(size_t)k * per + i];
+    out->probes = (int64_t)s[0];
+    out->overlaps = (int64_t)s[1];
+    out->below = (int64_t)s[2];
+    out->above = (int64_t)s[3];
+    out->pairs = (int64_t)s[4];
+    for (int b = 0; b < nbins; ++b) {
+        h_hist[b] = (uint64_t)s[(size_t)kProbeHead + (size_t)b];
+        h_esum[b] = (int64_t)s[(size_t)kProbeHead + (size_t)nbins + (size_t)b];
+    }
     return PMC_OK;
 }
 

@@ -27,6 +27,7 @@ struct pmc_ctx {
     unsigned long long* eacc = nullptr;    // kStatSlots (energy)
     int* segq = nullptr;                   // energy: queue of row segments over the staging capacity
     unsigned long long* pobs = nullptr;    // pair observables: accumulator copies (allocated on first use)
+    unsigned long long* probe_acc = nullptr;   // test-particle energies: accumulator copies (allocated on first use)
     uint32_t* flags = nullptr;
     int* ovf = nullptr;                    // subsweep overflow queue (1 + cells per colour)
     int* ovf_aux = nullptr;                // second queue: launches on a caller stream (pmc_phase_range_on)

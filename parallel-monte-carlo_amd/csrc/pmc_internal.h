@@ -165,6 +165,16 @@ constexpr int kPairObsMaxBins = 512;   // PMC_PAIROBS_MAX_BINS
 static_assert((kPairObsCopies & (kPairObsCopies - 1)) == 0, "accumulator copies: a power of two");
 hipError_t launch_pairobs(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc,
                           float rmax2, float bscale, int nbins, hipStream_t st);
+// test-particle energies (k_probe, pmc_probe.h): acc holds kProbeCopies accumulator copies of
+// kProbeHead + 2 * nbins counters each ([0] probes, [1] overlaps, [2] below, [3] above, [4] pairs, then
+// hist[nbins], then esum[nbins]), zeroed on st before the call; the host sums the copies.  lo4 / bw4:
+// pmc_probe_range's
+constexpr int kProbeCopies = 32;
+constexpr int kProbeHead = 5;
+constexpr int kProbeMaxBins = 512;   // PMC_PROBE_MAX_BINS
+static_assert((kProbeCopies & (kProbeCopies - 1)) == 0, "accumulator copies: a power of two");
+hipError_t launch_probe(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int mode,
+                        int k_per_cell, uint32_t sample, int64_t lo4, int64_t bw4, int nbins, hipStream_t st);
 // the cells of one colour of one plane: mode 0 plane -> packed buffer, 1 packed -> plane,
 // 2 plane -> plane; (cps_x/2)*(cps_y/2)*3*nmax floats
 hipError_t launch_colour_rows(const DevGeom& g, const float* src, float* dst, int colour, int mode, hipStream_t st);

@@ -26,6 +26,7 @@
 #include "pmc_internal.h"
 #include "../../include/pmc_detmath.h"
 #include "../../include/pmc_pairobs.h"
+#include "../../include/pmc_probe.h"
 
 namespace pmc {
 
@@ -2746,6 +2747,254 @@ __global__ __launch_bounds__(kWave) void k_pairobs(DevGeom g, const float* __res
 }
 
 // ------------------------------------------------------------------------------------------
+// test-particle energies (include/pmc_probe.h): per owned cell, kpc Widom insertions at Philox
+// positions (PMC_PROBE_INSERT) or the cell's own particles with their own slot skipped
+// (PMC_PROBE_REAL), each against the cell's 27-cell stencil.  k_pairobs' per-cell form: the same
+// stencil (pairobs_stencil), the same staging (rows of 8 slots, chunks for the fuller cells, own
+// cell first, the pmc_box_d2 filter -- exact for both modes: a probe lies inside the padded cell
+// box -- and the 27 * nmax LDS capacity), the same fixed grid of waves over runs of kPairObsRun
+// cells.  Per probe the lanes take the staged partners in blocks of 64 and keep an int64 sum of
+// the fixed-point terms outside the core; one DPP wave reduction, then the wave-uniform class
+// (below / bin / above) and lane 0 adds to the wave's private LDS histogram (u32 counts, int64
+// energy sums; a wave visits at most cells / 4096 + kPairObsRun cells of at most 64 probes, so a
+// count stays below 2^32).  One flush per wave with 64-bit global atomics into one of kProbeCopies
+// accumulator copies.  No beta, no exp; integer sums only, equal to tests/probe_ref.c bit for bit.
+// ------------------------------------------------------------------------------------------
+
+// one step of the int64 wave sum: v += (v moved by DPP control CTRL under row mask RM; 0 where no
+// lane is written)
+template <int CTRL, int RM>
+__device__ __forceinline__ long long dpp_add_i64(long long v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, RM, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)((unsigned long long)v >> 32), CTRL, RM, 0xF, false);
+    return (long long)((unsigned long long)v + (((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo));
+}
+// wave-wide int64 sum, wave-uniform: wave_sum_fixed_order_s' DPP steps (xor 1, 2, row half mirror,
+// row mirror, row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3) leave it in lane 63
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+    v = dpp_add_i64<0xB1, 0xF>(v);
+    v = dpp_add_i64<0x4E, 0xF>(v);
+    v = dpp_add_i64<0x141, 0xF>(v);
+    v = dpp_add_i64<0x140, 0xF>(v);
+    v = dpp_add_i64<0x142, 0xA>(v);
+    v = dpp_add_i64<0x143, 0xC>(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), 63);
+    return (long long)(((unsigned long long)hi << 32) | (unsigned long long)lo);
+}
+
+// pmc_probe_bin without a 64-bit division: the quotient of an in-range probe is below nbins <= 512,
+// so the float estimate d * inv_bw (inv_bw = 1 / (float)bw4; relative error < 2^-21) is within one
+// of it and one exact correction step settles it
+__device__ __forceinline__ int probe_bin_dev(long long e4, long long lo4, long long bw4, float inv_bw, int nbins) {
+    if (e4 < lo4) return -1;
+    const unsigned long long d = (unsigned long long)(e4 - lo4);
+    if (d >= (unsigned long long)nbins * (unsigned long long)bw4) return nbins;
+    int q = (int)((float)d * inv_bw);
+    const long long r = (long long)d - (long long)q * bw4;
+    q += r < 0 ? -1 : (r >= bw4 ? 1 : 0);
+    return q < 0 ? 0 : (q > nbins - 1 ? nbins - 1 : q);   // (never clamps; keeps the LDS index in range)
+}
+
+template <int NSLOT, bool OFF32>
+__global__ __launch_bounds__(kWave) void k_probe(DevGeom g, const float* __restrict__ disk,
+                                                 const int16_t* __restrict__ ncnt,
+                                                 unsigned long long* __restrict__ acc, uint32_t total_cells, int mode,
+                                                 int kpc, uint32_t sample, long long lo4, long long bw4, float inv_bw,
+                                                 int nbins) {
+    extern __shared__ __attribute__((aligned(16))) float psm[];
+    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
+    constexpr int CPP = kWave / HS;    // cells per staging pass
+    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
+    using DA = DiskAddr<OFF32>;
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int cap = 27 * nm;
+    long long* esum = (long long*)psm;             // nbins energy sums of this wave (8-byte aligned)
+    float* ex_ = psm + 2 * nbins;
+    float* ey_ = ex_ + cap;
+    float* ez_ = ex_ + 2 * cap;
+    int* inv_l = (int*)(ex_ + 3 * cap);            // list entry -> stencil lane (32 ints)
+    unsigned* hist = (unsigned*)(inv_l + 32);      // nbins counters of this wave
+    const int p = lane % HS;
+    const int ee = lane / HS;
+    const float rc2 = g.rc2;
+    const bool real = mode == PMC_PROBE_REAL;
+    unsigned long long n_probes = 0, n_over = 0, n_below = 0, n_above = 0, n_pairs = 0;   // wave-uniform
+    for (int b = lane; b < nbins; b += kWave) {
+        hist[b] = 0u;
+        esum[b] = 0;
+    }
+    if (lane < 32) inv_l[lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+
+    // rows of the cell in flight (k_pairobs' issue_rows): slots [0, HS) of its occupied stencil cells
+    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
+    bool vact[NPMAX];
+    int ncells = 0;
+    auto issue_rows = [&](const PairObsStencil& st) {
+        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
+        ncells = __popcll(mo);
+        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int q = 0; q < NPMAX; ++q) {
+            const int e = q * CPP + ee;
+            const int src = inv_l[e < ncells ? e : 0];
+            const int c_cnt = __shfl(st.cnt, src);
+            const int c_idx = __shfl(st.kc, src);
+            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
+            vact[q] = e < ncells && p < c_cnt;
+            vx[q] = vy[q] = vz[q] = 0.0f;
+            if (vact[q]) {
+                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
+                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
+                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
+                vy[q] = vy[q] + isy;
+                vz[q] = vz[q] + isz;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
+    };
+
+    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
+    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
+        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
+        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
+        issue_rows(cur);
+        PairObsStencil nxt = cur;
+        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
+        for (int c = 0; c < ncl; ++c) {
+            // ---- stage cell c (k_pairobs' staging): own particles first, then the filtered partners
+            float blo[3], bhi[3];
+            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
+            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
+            int S = 0;
+            auto put = [&](bool act, float ux, float uy, float uz) {
+                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+                if (act) {
+                    const int dst = S + mbcnt64(am);
+                    ex_[dst] = ux;
+                    ey_[dst] = uy;
+                    ez_[dst] = uz;
+                }
+                S += __popcll(am);
+            };
+            auto chunks = [&](unsigned long long mg, bool filter) {
+                if constexpr (NSLOT > HS) {
+                    for (int s0 = HS; s0 < nm; s0 += HS) {
+                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
+                        while (ov) {
+                            int ks = 0, nc = 0;
+                            for (; nc < CPP && ov; ++nc) {
+                                const int kb = (int)__builtin_ctzll(ov);
+                                ov &= ov - 1ull;
+                                ks = ee == nc ? kb : ks;
+                            }
+                            const int c_cnt = __shfl(cur.cnt, ks);
+                            const int c_idx = __shfl(cur.kc, ks);
+                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
+                            const int ps = s0 + p;
+                            const bool act = ee < nc && ps < c_cnt;
+                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+                            if (act) {
+                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
+                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+                                ux = ux + isx;
+                                uy = uy + isy;
+                                uz = uz + isz;
+                            }
+                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz);
+                        }
+                    }
+                }
+            };
+            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
+            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
+            const int cx = __builtin_amdgcn_readfirstlane(cur.x), cy = __builtin_amdgcn_readfirstlane(cur.y);
+            const int czg = __builtin_amdgcn_readfirstlane(cur.zg);
+            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0]);             // own slots [0, HS)
+            chunks(1ull, false);                                          // own slots [HS, n)
+#pragma unroll
+            for (int q = 0; q < NPMAX; ++q) {
+                const int e = q * CPP + ee;
+                if (q * CPP < ncells) put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q]);
+            }
+            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            // ---- the next cell's rows go out now and arrive while this cell's probes run
+            if (c + 1 < ncl) {
+                cur = nxt;
+                issue_rows(cur);
+                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
+            }
+            // ---- the probes: lane i holds probe i (REAL: the own particles, staged first)
+            const int nprobe = real ? n_own : kpc;
+            n_probes += (unsigned long long)nprobe;
+            float px, py, pz;
+            if (real) {
+                px = ex_[lane];
+                py = ey_[lane];
+                pz = ez_[lane];
+            } else {
+                const uint32_t gid = (uint32_t)cx + (uint32_t)g.cps_x * ((uint32_t)cy + (uint32_t)g.cps_y * (uint32_t)czg);
+                const pmc_u32x4 wd = philox_rare((uint32_t)lane, gid, sample, PMC_TAG_PROBE, g);
+                px = pmc_probe_coord(wd.v[0], cx, g.w, g.Lx);
+                py = pmc_probe_coord(wd.v[1], cy, g.w, g.Ly);
+                pz = pmc_probe_coord(wd.v[2], czg, g.w, g.Lz);
+            }
+            for (int i = 0; i < nprobe; ++i) {
+                const float xi = as_f(__builtin_amdgcn_readlane(as_i(px), i));
+                const float yi = as_f(__builtin_amdgcn_readlane(as_i(py), i));
+                const float zi = as_f(__builtin_amdgcn_readlane(as_i(pz), i));
+                long long sum = 0;                 // per lane
+                unsigned long long hard = 0;       // lanes with a partner inside the core
+                for (int jb = 0; jb < S; jb += kWave) {
+                    const int j = jb + lane;
+                    const bool vj = j < S && !(real && j == i);
+                    const int jj = j < S ? j : 0;
+                    const float r2 = pmc_r2(xi - ex_[jj], yi - ey_[jj], zi - ez_[jj]);
+                    const bool in = vj && r2 <= rc2;
+                    const unsigned long long im = __builtin_amdgcn_ballot_w64(in);
+                    if (im == 0ull) continue;
+                    n_pairs += (unsigned long long)__popcll(im);
+                    const bool core = in && r2 < PMC_PROBE_CORE_R2;
+                    hard |= __builtin_amdgcn_ballot_w64(core);
+                    const long long t = pmc_to_fixed_f32(pmc_lj4_from_r2(r2, rc2));
+                    sum += in && !core ? t : 0ll;
+                }
+                if (hard) {
+                    ++n_over;
+                    continue;
+                }
+                const long long e4 = wave_sum_i64(sum);
+                const int cls = __builtin_amdgcn_readfirstlane(probe_bin_dev(e4, lo4, bw4, inv_bw, nbins));
+                if (cls < 0) ++n_below;
+                else if (cls >= nbins) ++n_above;
+                else if (lane == 0) {
+                    hist[cls] += 1u;
+                    esum[cls] += e4;
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+        }
+    }
+    // ---- flush: the wave's counters and its nonzero bins
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kProbeCopies - 1)) * (size_t)(kProbeHead + 2 * nbins);
+    const unsigned long long head5 =
+        lane == 0 ? n_probes : (lane == 1 ? n_over : (lane == 2 ? n_below : (lane == 3 ? n_above : n_pairs)));
+    if (lane < kProbeHead && head5 != 0) atomicAdd(&mine[lane], head5);
+    for (int b = lane; b < nbins; b += kWave) {
+        const unsigned h = hist[b];
+        if (h) {
+            atomicAdd(&mine[kProbeHead + b], (unsigned long long)h);
+            atomicAdd(&mine[kProbeHead + nbins + b], (unsigned long long)esum[b]);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // self-test of the deterministic math on the device (compared bitwise with the host oracle)
 // ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
@@ -3592,6 +3841,28 @@ hipError_t launch_pairobs(const DevGeom& g, const float* disk, const int16_t* n,
         constexpr bool O = decltype(off)::value;
         hipLaunchKernelGGL((k_pairobs<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, rmax2, bscale,
                            nbins);
+    });
+    return hipGetLastError();
+}
+
+// acc: kProbeCopies copies of [probes, overlaps, below, above, pairs, hist[nbins], esum[nbins]], zeroed on
+// st before the call.  launch_pairobs' fixed grid; 11.2 KiB of LDS per wave at nmax 16 and 512 bins.
+hipError_t launch_probe(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int mode,
+                        int k_per_cell, uint32_t sample, int64_t lo4, int64_t bw4, int nbins, hipStream_t st) {
+    if (nbins < 1 || nbins > kProbeMaxBins || bw4 < 1) return hipErrorInvalidValue;
+    if (mode != PMC_PROBE_INSERT && mode != PMC_PROBE_REAL) return hipErrorInvalidValue;
+    if (mode == PMC_PROBE_INSERT && (k_per_cell < 1 || k_per_cell > PMC_PROBE_MAX_K)) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
+    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
+    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
+    const size_t lds = sizeof(float) * (3 * 27 * (size_t)g.nmax + 32 + 3 * (size_t)nbins);
+    const float inv_bw = 1.0f / (float)bw4;
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
+    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
+        hipLaunchKernelGGL((k_probe<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, mode, k_per_cell,
+                           sample, (long long)lo4, (long long)bw4, inv_bw, nbins);
     });
     return hipGetLastError();
 }

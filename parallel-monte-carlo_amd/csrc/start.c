@@ -4,7 +4,7 @@
  *
  *   start [--cps 4] [--atoms 64] [--passes 1000] [--nmax 16] [--moves 10] [--beta 0.3]
  *         [--sigma 0.5] [--w 2.5] [--seed 1234] [--every 1] [--graph]
- *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS]
+ *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS] [--widom K]
  *
  * --dump writes create_dump frames (kernel.cu:510-536; the reference's VISUALISATION path) of the
  * initial state and after every --every sweeps; --save writes a PMCSNAP1 snapshot at the end;
@@ -13,11 +13,15 @@
  * state (pmc_pair_observables, r_max = w): the g(r) table and one `pressure` line with the ideal part
  * N/(V beta), the virial part W/(3V) and the impulsive part of the truncated, unshifted potential,
  * (2 pi/3) rho^2 rc^3 g(rc) 4 (rc^-12 - rc^-6) with g(rc) from the last bin (negative).
+ * --widom K inserts K test particles per cell into the final state (pmc_probe_energies, 512 bins over
+ * [-32, 96), widened once to [-256, 768) if an insertion falls below the range) and prints one `widom`
+ * line: beta mu_ex = -ln <exp(-beta dU)> and the fraction of insertions that hit a hard core.
  *
  * Prints "step: energy" lines like kernel.cu:643,695 (energy from the cell-list sum every
  * --every sweeps) and a final summary with acceptance ratio and trial-moves/s.  Compile-time
  * #defines of the reference (start.cu:14-24) become runtime flags.
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -35,7 +39,7 @@ int main(int argc, char** argv) {
     p.cps_x = 4; p.nmax = 16; p.n_moves = 10;
     p.w = 2.5f; p.beta = 0.3f; p.sigma = 0.5f; p.seed = 1234;
     long long atoms = 64;
-    int passes = 1000, every = 1, graph = 0, pairobs = 0;
+    int passes = 1000, every = 1, graph = 0, pairobs = 0, widom = 0;
     const char *dump = NULL, *save = NULL, *restart = NULL;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -55,6 +59,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--save")) { save = v; ++i; }
         else if (!strcmp(a, "--restart")) { restart = v; ++i; }
         else if (!strcmp(a, "--pairobs")) { pairobs = atoi(v); ++i; }
+        else if (!strcmp(a, "--widom")) { widom = atoi(v); ++i; }
         else { fprintf(stderr, "unknown flag %s\n", a); return 2; }
     }
     if (every < 1) every = 1;
@@ -138,6 +143,30 @@ int main(int argc, char** argv) {
         printf("pressure %.9g ideal %.9g virial %.9g impulsive %.9g (N %lld, V %.6f, ordered pairs %lld)\n",
                p_ideal + p_vir + p_imp, p_ideal, p_vir, p_imp, (long long)po.particles, vol, (long long)po.pairs);
         free(hist);
+    }
+    if (widom) {
+        enum { NB = 512 };
+        static uint64_t hist[NB];
+        static int64_t esum[NB];
+        pmc_probe_obs po;
+        pmc_params q;
+        float e_lo = -32.0f, e_hi = 96.0f;
+        if ((rc = pmc_get_params(ctx, &q))) die("pmc_get_params", rc);
+        if ((rc = pmc_probe_energies(ctx, 0, widom, first + (uint32_t)passes, e_lo, e_hi, NB, hist, esum, &po)))
+            die("pmc_probe_energies", rc);
+        if (po.below > 0) {   /* an insertion below the range would be dropped with the largest weight */
+            e_lo = -256.0f; e_hi = 768.0f;
+            if ((rc = pmc_probe_energies(ctx, 0, widom, first + (uint32_t)passes, e_lo, e_hi, NB, hist, esum, &po)))
+                die("pmc_probe_energies", rc);
+        }
+        double avg = 0.0;
+        for (int b = 0; b < NB; ++b)
+            if (hist[b])
+                avg += (double)hist[b] * exp(-(double)q.beta * 4.0 * (double)esum[b] / ((double)hist[b] * 4294967296.0));
+        avg /= po.probes > 0 ? (double)po.probes : 1.0;
+        printf("widom beta_mu_ex %.9g overlap_fraction %.6f (insertions %lld, below %lld, above %lld, range %g %g)\n",
+               avg > 0.0 ? -log(avg) : INFINITY, po.probes ? (double)po.overlaps / (double)po.probes : 0.0,
+               (long long)po.probes, (long long)po.below, (long long)po.above, (double)e_lo, (double)e_hi);
     }
     pmc_destroy(ctx);
     return 0;

@@ -44,6 +44,13 @@ class PairObs(C.Structure):
     _fields_ = [("virial_fixed", C.c_int64), ("pairs", C.c_int64), ("particles", C.c_int64)]
 
 
+class ProbeObs(C.Structure):
+    """``pmc_probe_obs``."""
+
+    _fields_ = [("probes", C.c_int64), ("overlaps", C.c_int64), ("below", C.c_int64), ("above", C.c_int64),
+                ("pairs", C.c_int64)]
+
+
 class Result(C.Structure):
     """``pmc_result``."""
 
@@ -56,6 +63,7 @@ PMC_FLAG_QUIRK_R1, PMC_FLAG_QUIRK_R2, PMC_FLAG_QUIRK_S1 = 2, 4, 8     # referenc
 PMC_OK, PMC_ERR_ARG, PMC_ERR_HIP, PMC_ERR_OVERFLOW, PMC_ERR_RANGE, PMC_ERR_NODEV = 0, -1, -2, -3, -4, -5
 PMC_IPC_HANDLE_BYTES = 1024     # include/pmc.h
 PMC_LAYOUT_REFERENCE, PMC_LAYOUT_PACKED = 0, 1
+PMC_PROBE_INSERT, PMC_PROBE_REAL = 0, 1     # include/pmc_probe.h
 
 
 class PmcError(RuntimeError):
@@ -152,6 +160,8 @@ def lib():
              C.POINTER(C.c_int), C.POINTER(C.c_float))
         _sig(L, "pmc_energy", i32, _vp, C.POINTER(C.c_double))
         _sig(L, "pmc_pair_observables", i32, _vp, C.c_float, i32, _vp, C.POINTER(PairObs))
+        _sig(L, "pmc_probe_energies", i32, _vp, i32, i32, u32, C.c_float, C.c_float, i32, _vp, _vp,
+             C.POINTER(ProbeObs))
         _sig(L, "pmc_stats_read", i32, _vp, C.POINTER(Stats), i32)
         _sig(L, "pmc_error_flags", i32, _vp, C.POINTER(C.c_uint32), i32)
         _sig(L, "pmc_copy_out", i32, _vp, _vp, _vp)

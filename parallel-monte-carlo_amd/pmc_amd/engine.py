@@ -21,7 +21,8 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import PMC_IPC_HANDLE_BYTES, PairObs, Params, Result, Stats, check, lib
+from ._lib import (PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT, PMC_PROBE_REAL, PairObs, Params, ProbeObs, Result, Stats,
+                   check, lib)
 
 FIX_SCALE = 2.0 ** 32
 
@@ -302,6 +303,27 @@ class PmcContext:
                                          hist.ctypes.data if hist.size else None, C.byref(out)))
         return {"hist": hist, "virial_fixed": int(out.virial_fixed), "pairs": int(out.pairs),
                 "particles": int(out.particles)}
+
+    def probe_energies(self, mode="insert", k: int = 1, sample: int = 0, e_lo: float = -32.0, e_hi: float = 96.0,
+                       nbins: int = 512) -> dict:
+        """Test-particle energies (pmc_probe_energies, include/pmc_probe.h).  mode "insert" (or 0): k
+        Widom insertions per owned cell, drawn from (seed, cell, sample); mode "real" (or 1): every owned
+        particle probed at its own position (k and sample ignored).  Returns the integer sums: hist
+        (uint64) and esum (int64, quarter energies in 2^-32 units) over nbins bins of [e_lo, e_hi), and
+        probes, overlaps, below, above, pairs, with the range that was used.  Results of several calls
+        (samples, slab ranks) add key by key (observables.add_probe); observables.mu_excess and
+        observables.energy_distribution convert them."""
+        m = {"insert": PMC_PROBE_INSERT, "real": PMC_PROBE_REAL}.get(mode, mode)
+        hist = np.zeros(max(int(nbins), 0), np.uint64)
+        esum = np.zeros(max(int(nbins), 0), np.int64)
+        out = ProbeObs()
+        check("pmc_probe_energies",
+              lib().pmc_probe_energies(self._h, int(m), int(k), int(sample) & 0xFFFFFFFF, e_lo, e_hi, nbins,
+                                       hist.ctypes.data if hist.size else None,
+                                       esum.ctypes.data if esum.size else None, C.byref(out)))
+        res = {key: int(getattr(out, key)) for key, _ in ProbeObs._fields_}
+        res.update(hist=hist, esum=esum, e_lo=float(np.float32(e_lo)), e_hi=float(np.float32(e_hi)), mode=int(m))
+        return res
 
     def stats(self, reset: bool = False) -> dict:
         s = Stats()
