@@ -379,6 +379,23 @@ typedef struct pmc_probe_obs {
 } pmc_probe_obs;
 int pmc_probe_energies(pmc_ctx* ctx, int mode, int k_per_cell, uint32_t sample, float e_lo, float e_hi, int nbins,
                        uint64_t* h_hist, int64_t* h_esum, pmc_probe_obs* out);
+/* Collective density modes rho(k) = sum_j exp(i k.r_j) of the owned cells' particles at the
+ * reciprocal-lattice vectors k = 2 pi (h_x / L_x, h_y / L_y, h_z / L_z), defined bit for bit in
+ * pmc_sk.h (integer position words, an integer phase, fixed-point cos / sin terms); the static
+ * structure factor is S(k) = |rho(k)|^2 / N (pmc_amd.observables.structure_factor).  Unlike g(r)
+ * it is not bounded by the cutoff: it sees structure across the whole box.  h_hkl is a HOST
+ * pointer to nk integer triples (h_x, h_y, h_z); h_re / h_im are HOST pointers to nk int64 sums in
+ * 2^-32 units (rho = (re + i im) / 2^32).  The zero vector gives re = particles << 32, im = 0.
+ * PMC_ERR_ARG for a null pointer, nk outside 1..4096, any |h_d| > 1024, and for a slab context
+ * with a pending deferred z exchange (pmc_slab_finish first, as for pmc_energy).  Runs on the context
+ * stream and synchronises; state, statistics, error flags and the energy are left unchanged.  No
+ * cross-rank reduction: every output is an integer sum and the position words use global
+ * coordinates, so the caller adds the ranks' re, im and particles of ONE sample (rho of different
+ * samples must not be added: average S). */
+typedef struct pmc_sk_obs {
+    int64_t particles;  /* particles in owned cells */
+} pmc_sk_obs;
+int pmc_density_modes(pmc_ctx* ctx, const int32_t* h_hkl, int nk, int64_t* h_re, int64_t* h_im, pmc_sk_obs* out);
 /* Read and optionally reset the accumulated subsweep statistics (synchronises). */
 int pmc_stats_read(pmc_ctx* ctx, pmc_stats* out, int reset);
 /* Device error flags (bit 0: shift overflow, bit 1: assign overflow, bit 2: assign range, bits 3-4:

@@ -14,12 +14,14 @@
 #include "pmc_ctx.h"
 #include "../../include/pmc_pairobs.h"
 #include "../../include/pmc_probe.h"
+#include "../../include/pmc_sk.h"
 
 using namespace pmc;
 using namespace pmc_sched;
 
 static_assert(kPairObsMaxBins == PMC_PAIROBS_MAX_BINS, "pair observables: bin cap");
 static_assert(kProbeMaxBins == PMC_PROBE_MAX_BINS, "test-particle energies: bin cap");
+static_assert(kSkMaxK == PMC_SK_MAX_K, "density modes: vector cap");
 
 int pmc::issue_phases(pmc_ctx* c, hipStream_t st, int* ovf, unsigned long long* stats, int z0, int z1, uint32_t sweep,
                       const pmc_sweep_plan_t& plan, int k0, int k1, PhaseKind kind, float* mirror, int64_t phase0) {
@@ -304,6 +306,7 @@ void pmc_destroy(pmc_ctx* c) {
     if (c->segq) (void)hipFree(c->segq);
     if (c->pobs) (void)hipFree(c->pobs);
     if (c->probe_acc) (void)hipFree(c->probe_acc);
+    if (c->sk_acc) (void)hipFree(c->sk_acc);
     if (c->flags) (void)hipFree(c->flags);
     if (c->ovf) (void)hipFree(c->ovf);
     if (c->ovf_aux) (void)hipFree(c->ovf_aux);
@@ -735,6 +738,46 @@ int pmc_probe_energies(pmc_ctx* c, int mode, int k_per_cell, uint32_t sample, fl
     for (int b = 0; b < nbins; ++b) {
         h_hist[b] = (uint64_t)s[(size_t)kProbeHead + (size_t)b];
         h_esum[b] = (int64_t)s[(size_t)kProbeHead + (size_t)nbins + (size_t)b];
+    }
+    return PMC_OK;
+}
+
+int pmc_density_modes(pmc_ctx* c, const int32_t* h_hkl, int nk, int64_t* h_re, int64_t* h_im, pmc_sk_obs* out) {
+    if (!c || !h_hkl || !h_re || !h_im || !out) return fail(PMC_ERR_ARG, "bad argument");
+    if (nk < 1 || nk > PMC_SK_MAX_K) return fail(PMC_ERR_ARG, "pmc_density_modes: nk must be in 1..4096");
+    for (int i = 0; i < 3 * nk; ++i)
+        if (h_hkl[i] > PMC_SK_MAX_H || h_hkl[i] < -PMC_SK_MAX_H)
+            return fail(PMC_ERR_ARG, "pmc_density_modes: every |h| must be <= 1024");
+    // the same rule as the observables that read the halos (energy_fixed): one state per sample on every rank
+    if (slab_pending_zdir(c))
+        return fail(PMC_ERR_ARG, "pmc_density_modes: a slab halo exchange is pending (call pmc_slab_finish first)");
+    if (int rj = slab_join(c)) return rj;
+    const size_t per = (size_t)kSkHead + 2 * (size_t)nk;
+    if (nk > c->sk_cap) {   // allocated on first use, grown with nk: the accumulator copies, then the vectors
+        if (c->sk_acc) {
+            PMC_HIP(hipStreamSynchronize(c->stream));
+            PMC_HIP(hipFree(c->sk_acc));
+            c->sk_acc = nullptr;
+            c->sk_cap = 0;
+        }
+        PMC_HIP(hipMalloc(&c->sk_acc, sizeof(unsigned long long) * kSkCopies * per + sizeof(int32_t) * 3 * (size_t)nk));
+        c->sk_cap = nk;
+    }
+    int* d_hkl = (int*)(c->sk_acc + (size_t)kSkCopies * per);
+    PMC_HIP(hipMemsetAsync(c->sk_acc, 0, sizeof(unsigned long long) * kSkCopies * per, c->stream));
+    PMC_HIP(hipMemcpyAsync(d_hkl, h_hkl, sizeof(int32_t) * 3 * (size_t)nk, hipMemcpyHostToDevice, c->stream));
+    hipError_t e = launch_sk(c->G, c->disk[c->cur], c->n[c->cur], c->sk_acc, d_hkl, nk, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "density modes launch");
+    std::vector<unsigned long long> h((size_t)kSkCopies * per);
+    PMC_HIP(hipMemcpyAsync(h.data(), c->sk_acc, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    std::vector<unsigned long long> s(per, 0ull);
+    for (int k = 0; k < kSkCopies; ++k)
+        for (size_t i = 0; i < per; ++i) s[i] += h[(size_t)k * per + i];
+    out->particles = (int64_t)s[0];
+    for (int m = 0; m < nk; ++m) {
+        h_re[m] = (int64_t)s[(size_t)kSkHead + (size_t)m];
+        h_im[m] = (int64_t)s[(size_t)kSkHead + (size_t)nk + (size_t)m];
     }
     return PMC_OK;
 }

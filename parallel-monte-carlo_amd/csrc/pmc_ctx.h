@@ -28,8 +28,10 @@ struct pmc_ctx {
     int* segq = nullptr;                   // energy: queue of row segments over the staging capacity
     unsigned long long* pobs = nullptr;    // pair observables: accumulator copies (allocated on first use)
     unsigned long long* probe_acc = nullptr;   // test-particle energies: accumulator copies (allocated on first use)
+    unsigned long long* sk_acc = nullptr;      // density modes: accumulator copies, then the vectors (grown with nk)
+    int sk_cap = 0;                            // vectors sk_acc has room for
     uint32_t* flags = nullptr;
-    int* ovf = nullptr;                    // subsweep overflow queue (1 + cells per colour)
+    int* ovf = nullptr;                   // subsweep overflow queue (1 + cells per colour)
     int* ovf_aux = nullptr;                // second queue: launches on a caller stream (pmc_phase_range_on)
     int* ovf_b = nullptr;                  // third queue: the slab driver's boundary chain
     int* ovf_aux2 = nullptr;               // fourth queue: the slab driver's third interior chain

@@ -175,6 +175,16 @@ constexpr int kProbeMaxBins = 512;   // PMC_PROBE_MAX_BINS
 static_assert((kProbeCopies & (kProbeCopies - 1)) == 0, "accumulator copies: a power of two");
 hipError_t launch_probe(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int mode,
                         int k_per_cell, uint32_t sample, int64_t lo4, int64_t bw4, int nbins, hipStream_t st);
+// density modes (k_sk, pmc_sk.h): acc holds kSkCopies accumulator copies of kSkHead + 2 * nk counters
+// each ([0] owned particles, then re[nk], then im[nk]), zeroed on st before the call; the host sums the
+// copies.  hkl: nk (h_x, h_y, h_z) triples in DEVICE memory
+constexpr int kSkCopies = 32;
+constexpr int kSkHead = 1;
+constexpr int kSkMaxK = 4096;   // PMC_SK_MAX_K
+constexpr int kSkRun = 8;       // consecutive owned cells per wave and stride step
+static_assert((kSkCopies & (kSkCopies - 1)) == 0, "accumulator copies: a power of two");
+hipError_t launch_sk(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, const int* hkl,
+                     int nk, hipStream_t st);
 // the cells of one colour of one plane: mode 0 plane -> packed buffer, 1 packed -> plane,
 // 2 plane -> plane; (cps_x/2)*(cps_y/2)*3*nmax floats
 hipError_t launch_colour_rows(const DevGeom& g, const float* src, float* dst, int colour, int mode, hipStream_t st);

@@ -27,6 +27,7 @@
 #include "../../include/pmc_detmath.h"
 #include "../../include/pmc_pairobs.h"
 #include "../../include/pmc_probe.h"
+#include "../../include/pmc_sk.h"
 
 namespace pmc {
 
@@ -2995,6 +2996,102 @@ __global__ __launch_bounds__(kWave) void k_probe(DevGeom g, const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------
+// density modes (include/pmc_sk.h): rho(k) = sum_j exp(i k.r_j) over the owned cells' particles for
+// nk reciprocal-lattice vectors.  The other way round from every kernel above: the LANES are wave
+// vectors (blockIdx.y: blocks of 64), the particles are wave-uniform, and there is no stencil.  A
+// fixed grid of waves (blockIdx.x, launch_pairobs' shape) strides over runs of kSkRun owned cells.
+// Per run the lanes load the counts and the occupied slots (NSLOT lanes per cell), turn each
+// particle into its three position words once and compact them into LDS (12 B per particle, room
+// for a run); then the wave walks the staged particles -- one same-address LDS read per particle,
+// a broadcast -- and every lane adds its own term (three integer multiply-adds, shift, convert,
+// sincos, two fixed-point conversions, two 64-bit adds) to its two int64 accumulators, which stay
+// in registers for the wave's whole life.  No wave reduction, no filter, no exp.
+// Folded form (nk <= 32, P = 2^lgp >= nk): lane l takes vector l % P and the staged particles with
+// index = l / P modulo 64 / P; the flush's atomics add the groups.  lgp = 6 is the plain form.
+// One flush per wave: lane l adds vector l's sums with contiguous 64-bit global atomics into one of
+// kSkCopies accumulator copies of [particles, re[nk], im[nk]]; blockIdx.y == 0 counts the particles.
+// Integer sums only, equal to tests/sk_ref.c bit for bit.
+// ------------------------------------------------------------------------------------------
+template <int NSLOT, bool OFF32>
+__global__ __launch_bounds__(kWave) void k_sk(DevGeom g, const float* __restrict__ disk,
+                                              const int16_t* __restrict__ ncnt,
+                                              unsigned long long* __restrict__ acc, uint32_t total_cells,
+                                              const int* __restrict__ hkl, int nk, int lgp, float scx, float scy,
+                                              float scz) {
+    extern __shared__ __attribute__((aligned(16))) float psm[];
+    constexpr int CPP = kWave / NSLOT;        // cells per staging pass
+    constexpr int NPASS = kSkRun / CPP;       // passes per run (NSLOT / 8)
+    static_assert(NPASS >= 1 && NPASS * CPP == kSkRun, "a run is a whole number of staging passes");
+    using DA = DiskAddr<OFF32>;
+    uint32_t* sq = (uint32_t*)psm;            // staged words: particle j at 3 * j (kSkRun * nmax particles)
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int grp = lane >> lgp;              // folded form: the lane's particle residue
+    const int ngrp = kWave >> lgp;
+    const int vec = (int)blockIdx.y * kWave + (lane & ((1 << lgp) - 1));
+    const bool live = vec < nk;
+    int hx = 0, hy = 0, hz = 0;
+    if (live) {
+        hx = hkl[3 * vec];
+        hy = hkl[3 * vec + 1];
+        hz = hkl[3 * vec + 2];
+    }
+    long long re = 0, im = 0;                 // per lane
+    unsigned long long n_part = 0;            // wave-uniform
+    const int slot = lane % NSLOT;
+    const int ce = lane / NSLOT;
+    const uint32_t first = (uint32_t)g.halo * (uint32_t)(g.cps_x * g.cps_y);   // owned cells are storage cells first + t
+    const uint32_t stride = gridDim.x * (uint32_t)kSkRun;
+    for (uint32_t base = blockIdx.x * (uint32_t)kSkRun; base < total_cells; base += stride) {
+        const int ncl = (int)(total_cells - base < (uint32_t)kSkRun ? total_cells - base : (uint32_t)kSkRun);
+        int S = 0;
+#pragma unroll
+        for (int q = 0; q < NPASS; ++q) {
+            const int ci = q * CPP + ce;
+            bool act = false;
+            float x = 0.0f, y = 0.0f, z = 0.0f;
+            if (ci < ncl) {
+                const uint32_t cell = first + base + (uint32_t)ci;
+                int cnt = (int)ncnt[cell];
+                cnt = cnt < 0 ? 0 : (cnt > nm ? nm : cnt);
+                act = slot < cnt;
+                if (act) {
+                    const uint32_t off = (cell * (uint32_t)(3 * nm) + (uint32_t)slot * lay_slot()) * DA::kUnit;
+                    DA::ld3(disk, off, lay_dim(nm), x, y, z);
+                }
+            }
+            const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+            if (act) {
+                const int dst = 3 * (S + mbcnt64(am));
+                sq[dst] = pmc_sk_word(x, scx);
+                sq[dst + 1] = pmc_sk_word(y, scy);
+                sq[dst + 2] = pmc_sk_word(z, scz);
+            }
+            S += __popcll(am);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        n_part += (unsigned long long)S;
+        for (int jb = 0; jb < S; jb += ngrp) {
+            const int j = jb + grp;
+            const bool on = j < S;
+            const int jj = on ? j : 0;
+            int64_t a, b;
+            pmc_sk_term_unit(pmc_sk_phase(hx, hy, hz, sq[3 * jj], sq[3 * jj + 1], sq[3 * jj + 2]), &a, &b);
+            re += on ? (long long)a : 0ll;
+            im += on ? (long long)b : 0ll;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next run's staging overwrites sq
+    }
+    // ---- flush
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kSkCopies - 1)) * (size_t)(kSkHead + 2 * nk);
+    if (blockIdx.y == 0 && lane == 0 && n_part != 0) atomicAdd(&mine[0], n_part);
+    if (live) {
+        atomicAdd(&mine[kSkHead + vec], (unsigned long long)re);
+        atomicAdd(&mine[kSkHead + nk + vec], (unsigned long long)im);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // self-test of the deterministic math on the device (compared bitwise with the host oracle)
 // ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
@@ -3863,6 +3960,31 @@ hipError_t launch_probe(const DevGeom& g, const float* disk, const int16_t* n, u
         constexpr bool O = decltype(off)::value;
         hipLaunchKernelGGL((k_probe<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, mode, k_per_cell,
                            sample, (long long)lo4, (long long)bw4, inv_bw, nbins);
+    });
+    return hipGetLastError();
+}
+
+// acc: kSkCopies copies of [particles, re[nk], im[nk]], zeroed on st before the call; hkl: nk triples
+// in device memory.  launch_pairobs' fixed grid in x (at most 4096 waves), blocks of 64 vectors in
+// y; nk <= 32 takes the folded form with P the power of two >= nk.  12 B of LDS per particle of a
+// run: 1.5 KiB per wave at nmax 16.
+hipError_t launch_sk(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, const int* hkl,
+                     int nk, hipStream_t st) {
+    if (nk < 1 || nk > kSkMaxK) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
+    const int64_t runs = (total + kSkRun - 1) / kSkRun;
+    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096), (unsigned)((nk + kWave - 1) / kWave)), block(kWave);
+    const size_t lds = sizeof(uint32_t) * 3 * (size_t)kSkRun * (size_t)g.nmax;
+    int lgp = 6;
+    if (nk <= 32)
+        for (lgp = 0; (1 << lgp) < nk; ++lgp) {}
+    const float scx = pmc_sk_scale(g.Lx), scy = pmc_sk_scale(g.Ly), scz = pmc_sk_scale(g.Lz);
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_probe
+    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
+        hipLaunchKernelGGL((k_sk<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, hkl, nk, lgp, scx,
+                           scy, scz);
     });
     return hipGetLastError();
 }

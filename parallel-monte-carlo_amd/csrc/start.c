@@ -5,6 +5,7 @@
  *   start [--cps 4] [--atoms 64] [--passes 1000] [--nmax 16] [--moves 10] [--beta 0.3]
  *         [--sigma 0.5] [--w 2.5] [--seed 1234] [--every 1] [--graph]
  *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS] [--widom K]
+ *         [--sk HMAX]
  *
  * --dump writes create_dump frames (kernel.cu:510-536; the reference's VISUALISATION path) of the
  * initial state and after every --every sweeps; --save writes a PMCSNAP1 snapshot at the end;
@@ -16,6 +17,9 @@
  * --widom K inserts K test particles per cell into the final state (pmc_probe_energies, 512 bins over
  * [-32, 96), widened once to [-256, 768) if an insertion falls below the range) and prints one `widom`
  * line: beta mu_ex = -ln <exp(-beta dU)> and the fraction of insertions that hit a hard core.
+ * --sk HMAX (<= 1024) evaluates the density modes of the final state (pmc_density_modes) at (h,0,0),
+ * (0,h,0), (0,0,h) for h = 1..HMAX and prints one `sk` line per h with |k| = 2 pi h / L and the mean
+ * of the three S(k) = |rho(k)|^2 / N, then a closing `structure` line with N.
  *
  * Prints "step: energy" lines like kernel.cu:643,695 (energy from the cell-list sum every
  * --every sweeps) and a final summary with acceptance ratio and trial-moves/s.  Compile-time
@@ -39,7 +43,7 @@ int main(int argc, char** argv) {
     p.cps_x = 4; p.nmax = 16; p.n_moves = 10;
     p.w = 2.5f; p.beta = 0.3f; p.sigma = 0.5f; p.seed = 1234;
     long long atoms = 64;
-    int passes = 1000, every = 1, graph = 0, pairobs = 0, widom = 0;
+    int passes = 1000, every = 1, graph = 0, pairobs = 0, widom = 0, sk = 0;
     const char *dump = NULL, *save = NULL, *restart = NULL;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -60,9 +64,11 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--restart")) { restart = v; ++i; }
         else if (!strcmp(a, "--pairobs")) { pairobs = atoi(v); ++i; }
         else if (!strcmp(a, "--widom")) { widom = atoi(v); ++i; }
+        else if (!strcmp(a, "--sk")) { sk = atoi(v); ++i; }
         else { fprintf(stderr, "unknown flag %s\n", a); return 2; }
     }
     if (every < 1) every = 1;
+    if (sk < 0 || sk > 1024) { fprintf(stderr, "--sk HMAX: 1..1024\n"); return 2; }
 
     pmc_ctx* ctx = NULL;
     int rc = pmc_create(&p, &ctx);
@@ -167,6 +173,35 @@ int main(int argc, char** argv) {
         printf("widom beta_mu_ex %.9g overlap_fraction %.6f (insertions %lld, below %lld, above %lld, range %g %g)\n",
                avg > 0.0 ? -log(avg) : INFINITY, po.probes ? (double)po.overlaps / (double)po.probes : 0.0,
                (long long)po.probes, (long long)po.below, (long long)po.above, (double)e_lo, (double)e_hi);
+    }
+    if (sk) {
+        const double two_pi = 6.28318530717958647692;
+        int32_t* hkl = calloc(9 * (size_t)sk, sizeof(int32_t));
+        int64_t* re = calloc(3 * (size_t)sk, sizeof(int64_t));
+        int64_t* im = calloc(3 * (size_t)sk, sizeof(int64_t));
+        pmc_sk_obs so;
+        pmc_params q;
+        if (!hkl || !re || !im) die("calloc", 0);
+        if ((rc = pmc_get_params(ctx, &q))) die("pmc_get_params", rc);
+        for (int h = 1; h <= sk; ++h)
+            for (int d = 0; d < 3; ++d) hkl[9 * (h - 1) + 3 * d + d] = h;   /* (h,0,0), (0,h,0), (0,0,h) */
+        if ((rc = pmc_density_modes(ctx, hkl, 3 * sk, re, im, &so))) die("pmc_density_modes", rc);
+        const double len[3] = {(double)((float)q.cps_x * q.w), (double)((float)q.cps_y * q.w),
+                               (double)((float)q.cps_z * q.w)};
+        printf("# S(k): h, mean |k| of (h,0,0), (0,h,0), (0,0,h), mean S\n");
+        for (int h = 1; h <= sk; ++h) {
+            double k = 0.0, s = 0.0;
+            for (int d = 0; d < 3; ++d) {
+                const double a = (double)re[3 * (h - 1) + d] / 4294967296.0, b = (double)im[3 * (h - 1) + d] / 4294967296.0;
+                k += two_pi * h / len[d] / 3.0;
+                s += so.particles > 0 ? (a * a + b * b) / (double)so.particles / 3.0 : 0.0;
+            }
+            printf("sk %d %.9g %.9g\n", h, k, s);
+        }
+        printf("structure N %lld vectors %d\n", (long long)so.particles, 3 * sk);
+        free(hkl);
+        free(re);
+        free(im);
     }
     pmc_destroy(ctx);
     return 0;

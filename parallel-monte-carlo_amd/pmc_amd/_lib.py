@@ -51,6 +51,12 @@ class ProbeObs(C.Structure):
                 ("pairs", C.c_int64)]
 
 
+class SkObs(C.Structure):
+    """``pmc_sk_obs``."""
+
+    _fields_ = [("particles", C.c_int64)]
+
+
 class Result(C.Structure):
     """``pmc_result``."""
 
@@ -64,6 +70,7 @@ PMC_OK, PMC_ERR_ARG, PMC_ERR_HIP, PMC_ERR_OVERFLOW, PMC_ERR_RANGE, PMC_ERR_NODEV
 PMC_IPC_HANDLE_BYTES = 1024     # include/pmc.h
 PMC_LAYOUT_REFERENCE, PMC_LAYOUT_PACKED = 0, 1
 PMC_PROBE_INSERT, PMC_PROBE_REAL = 0, 1     # include/pmc_probe.h
+PMC_SK_MAX_K, PMC_SK_MAX_H = 4096, 1024     # include/pmc_sk.h
 
 
 class PmcError(RuntimeError):
@@ -162,6 +169,7 @@ def lib():
         _sig(L, "pmc_pair_observables", i32, _vp, C.c_float, i32, _vp, C.POINTER(PairObs))
         _sig(L, "pmc_probe_energies", i32, _vp, i32, i32, u32, C.c_float, C.c_float, i32, _vp, _vp,
              C.POINTER(ProbeObs))
+        _sig(L, "pmc_density_modes", i32, _vp, _vp, i32, _vp, _vp, C.POINTER(SkObs))
         _sig(L, "pmc_stats_read", i32, _vp, C.POINTER(Stats), i32)
         _sig(L, "pmc_error_flags", i32, _vp, C.POINTER(C.c_uint32), i32)
         _sig(L, "pmc_copy_out", i32, _vp, _vp, _vp)

@@ -21,8 +21,8 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT, PMC_PROBE_REAL, PairObs, Params, ProbeObs, Result, Stats,
-                   check, lib)
+from ._lib import (PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT, PMC_PROBE_REAL, PairObs, Params, ProbeObs, Result, SkObs,
+                   Stats, check, lib)
 
 FIX_SCALE = 2.0 ** 32
 
@@ -324,6 +324,30 @@ class PmcContext:
         res = {key: int(getattr(out, key)) for key, _ in ProbeObs._fields_}
         res.update(hist=hist, esum=esum, e_lo=float(np.float32(e_lo)), e_hi=float(np.float32(e_hi)), mode=int(m))
         return res
+
+    def density_modes(self, hkl) -> dict:
+        """Collective density modes rho(k) = sum_j exp(i k.r_j) of the owned cells' particles
+        (pmc_density_modes, include/pmc_sk.h) at k = 2 pi (h_x / L_x, h_y / L_y, h_z / L_z) for the
+        (nk, 3) integer array hkl (nk in 1..4096, every |h| <= 1024).  Returns hkl (int32), re and im
+        (int64 sums in 2^-32 units: rho = (re + i im) / 2^32), particles, and the box lengths L as
+        float32.  The ranks of ONE sample add exactly (observables.add_modes);
+        observables.structure_factor gives S(k) = |rho|^2 / N, which is what is averaged over samples."""
+        h = np.array(hkl)
+        if h.ndim != 2 or h.shape[1] != 3 or not np.issubdtype(h.dtype, np.integer):
+            raise ValueError("density_modes: hkl must be an (nk, 3) integer array")
+        if h.size and int(np.abs(h.astype(np.int64)).max()) >= 2 ** 31:
+            raise ValueError("density_modes: hkl out of range")
+        h = np.ascontiguousarray(h, np.int32)
+        nk = h.shape[0]
+        re = np.zeros(nk, np.int64)
+        im = np.zeros(nk, np.int64)
+        out = SkObs()
+        check("pmc_density_modes",
+              lib().pmc_density_modes(self._h, h.ctypes.data if nk else None, nk, re.ctypes.data if nk else None,
+                                      im.ctypes.data if nk else None, C.byref(out)))
+        w = np.float32(self.w)
+        L = np.array([np.float32(self.cps_x) * w, np.float32(self.cps_y) * w, np.float32(self.cps_z) * w], np.float32)
+        return {"hkl": h, "re": re, "im": im, "particles": int(out.particles), "L": L}
 
     def stats(self, reset: bool = False) -> dict:
         s = Stats()

@@ -1,7 +1,8 @@
 """Pressure and radial distribution function from the integer sums of
 ``PmcContext.pair_observables`` (pmc_pair_observables, include/pmc_pairobs.h), and the excess
 chemical potential and energy distributions from those of ``PmcContext.probe_energies``
-(pmc_probe_energies, include/pmc_probe.h).
+(pmc_probe_energies, include/pmc_probe.h), and the static structure factor S(k) from the density
+modes of ``PmcContext.density_modes`` (pmc_density_modes, include/pmc_sk.h).
 
 Pure numpy, no GPU: the sums of several slab contexts are added first (they are exact integers),
 then converted here.  Units are the library's reduced Lennard-Jones units (epsilon = sigma_LJ = 1).
@@ -109,3 +110,62 @@ def energy_distribution(res: dict) -> tuple:
     centres = 4.0 * lo4 / FIX_SCALE + (np.arange(len(res["hist"])) + 0.5) * width
     hist = np.asarray(res["hist"], np.float64)
     return centres, hist / (max(int(res["probes"]), 1) * width)
+
+
+# ---- density modes and S(k) (PmcContext.density_modes, include/pmc_sk.h) ------------------------
+
+def wave_vectors(h_max: int, half_space: bool = True) -> np.ndarray:
+    """All non-zero integer triples (h_x, h_y, h_z) with max |h_d| <= h_max as an (nk, 3) int32
+    array, in lexicographic order.  half_space keeps one of each +-h pair (S(-k) = S(k)): the one
+    whose first non-zero component is positive."""
+    r = np.arange(-int(h_max), int(h_max) + 1, dtype=np.int32)
+    h = np.stack(np.meshgrid(r, r, r, indexing="ij"), -1).reshape(-1, 3)
+    h = h[np.any(h != 0, axis=1)]
+    if half_space:
+        first = h[np.arange(len(h)), np.argmax(h != 0, axis=1)]
+        h = h[first > 0]
+    return np.ascontiguousarray(h, np.int32)
+
+
+def add_modes(a: dict, b: dict) -> dict:
+    """Sum of two density-mode results over the same vectors and box: the slab ranks of ONE sample
+    (every entry is an exact integer sum).  Results of different samples must NOT be added -- rho
+    of independent configurations averages to nothing; average structure_factor's S instead."""
+    if not np.array_equal(a["hkl"], b["hkl"]) or not np.array_equal(a["L"], b["L"]):
+        raise ValueError("add_modes: results over different wave vectors or box lengths")
+    out = dict(a)
+    out["re"] = np.asarray(a["re"], np.int64) + np.asarray(b["re"], np.int64)
+    out["im"] = np.asarray(a["im"], np.int64) + np.asarray(b["im"], np.int64)
+    out["particles"] = int(a["particles"]) + int(b["particles"])
+    return out
+
+
+def structure_factor(res: dict) -> tuple:
+    """(|k|, S) in float64 from a density-mode result of the WHOLE box (slab ranks added first,
+    add_modes): |k| from k_d = 2 pi h_d / L_d, S = (re^2 + im^2) / 2^64 / particles.  re and im are
+    scaled to float64 before squaring (|re| can reach N * 2^32: the square does not fit int64).
+    This is S of one configuration; the ensemble average is the mean of S over samples, taken by
+    the caller -- never the S of added rho."""
+    if res["particles"] <= 0:
+        raise ValueError("structure_factor: no particles")
+    h = np.asarray(res["hkl"], np.float64)
+    k = np.sqrt(((2.0 * np.pi * h / np.asarray(res["L"], np.float64)) ** 2).sum(axis=1))
+    re = np.asarray(res["re"], np.int64).astype(np.float64) / FIX_SCALE
+    im = np.asarray(res["im"], np.int64).astype(np.float64) / FIX_SCALE
+    return k, (re * re + im * im) / float(res["particles"])
+
+
+def shell_average(k, s, dk: float) -> tuple:
+    """(bin centres, mean S, counts) over the shells [b * dk, (b + 1) * dk) of |k|, for the occupied
+    shells up to the largest |k|; empty shells get a mean of nan."""
+    k = np.asarray(k, np.float64)
+    s = np.asarray(s, np.float64)
+    if not dk > 0:
+        raise ValueError("shell_average: dk must be positive")
+    b = np.floor(k / dk).astype(np.int64)
+    nb = int(b.max()) + 1 if b.size else 0
+    counts = np.bincount(b, minlength=nb)
+    sums = np.bincount(b, weights=s, minlength=nb)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(counts > 0, sums / counts, np.nan)
+    return (np.arange(nb) + 0.5) * dk, mean, counts
