@@ -396,6 +396,51 @@ typedef struct pmc_sk_obs {
     int64_t particles;  /* particles in owned cells */
 } pmc_sk_obs;
 int pmc_density_modes(pmc_ctx* ctx, const int32_t* h_hkl, int nk, int64_t* h_re, int64_t* h_im, pmc_sk_obs* out);
+/* ---- grand-canonical exchange moves (mu V T) ------------------------------------------------
+ * Insertions and deletions as a further kind of colour phase, defined bit for bit in pmc_gc.h: every
+ * owned cell of the colour runs k_per_cell (1..64) attempts in order on its own particle list, each
+ * an insertion at a Philox-drawn point of the cell or the deletion of a Philox-picked particle,
+ * accepted with min(1, z V_c / (n + 1) exp(-beta dU)) resp. its reciprocal; `activity` is
+ * z = exp(beta mu) / Lambda^3, a finite float > 0.  The reference samples fixed N only
+ * (start.cu:237-260 has displacement phases and shiftCells, nothing else).  The counters accumulate
+ * in the context until pmc_gc_stats_read resets them; they are not part of PMCSNAP1 snapshots
+ * (a further header field would change what PMCSNAP1 readers parse): a restarted run starts them at
+ * zero.  The state itself, counts included, is saved as before. */
+typedef struct pmc_gc_stats {
+    int64_t ins_trials;    /* insert attempts, full cells included */
+    int64_t ins_accepted;
+    int64_t ins_full;      /* insert attempts into a cell holding nmax particles (rejected) */
+    int64_t del_trials;    /* delete attempts, empty cells included */
+    int64_t del_accepted;
+    int64_t del_empty;     /* delete attempts in an empty cell (rejected) */
+    int64_t hard;          /* hard probes: inserts with a partner at r2 < 0.25 (rejected), deletes (accepted) */
+    int64_t de_fixed;      /* sum of the accepted moves' dU, fixed point 2^-32 energy units (exact) */
+    int64_t dn;            /* accepted inserts minus accepted deletes */
+} pmc_gc_stats;
+/* One exchange phase of colour id 0..7 (itoa, as pmc_phase) on the context state, in place on the
+ * current buffer; asynchronous on the context stream.  Whole-box and halo = 1 contexts: only owned
+ * cells act, halo cells are partners only, and afterwards the caller owes a halo refresh
+ * (pmc_slab_exchange) before anything reads the halos.  PMC_ERR_ARG for a colour outside 0..7,
+ * k_per_cell outside 1..64, an activity that is not finite and > 0 or whose table leaves pmc_logf's
+ * domain, halo = 2, the R1 / R2 quirk flags and a pending deferred z exchange (pmc_slab_finish
+ * first). */
+int pmc_exchange_phase(pmc_ctx* ctx, int colour, uint32_t sweep, float activity, int k_per_cell);
+/* The 8 colours in pmc_sweep_plan_ex's order for `sweep`.  On a context with the slab driver
+ * attached it is collective: a pending z exchange is flushed first and every phase is followed by
+ * pmc_slab_exchange (8 exchanges: simple and exact, not fast).  A slab context without the driver
+ * is refused (PMC_ERR_ARG): run the phases and the halo refreshes yourself. */
+int pmc_exchange_sweep(pmc_ctx* ctx, uint32_t sweep, float activity, int k_per_cell);
+/* Read and optionally reset the accumulated exchange counters (synchronises). */
+int pmc_gc_stats_read(pmc_ctx* ctx, pmc_gc_stats* out, int reset);
+/* Particles in the owned cells, counts clamped to [0, nmax] as the observables read them
+ * (synchronises). */
+int pmc_particle_count(pmc_ctx* ctx, int64_t* n);
+/* pmc_start with exchange sweeps (whole box only): for s = first_sweep .. first_sweep+mc_passes-1
+ * pmc_sweep(s), then pmc_exchange_sweep(s, ...) whenever (s + 1) % gc_every == 0 (gc_every >= 1).
+ * *gc (may be NULL) receives the run's exchange counters; e_initial + (out->stats.de_fixed +
+ * gc->de_fixed) / 2^32 equals e_final up to the float rounding of the displacement moves. */
+int pmc_start_gc(pmc_ctx* ctx, uint32_t first_sweep, int mc_passes, int gc_every, float activity, int k_per_cell,
+                 pmc_result* out, pmc_gc_stats* gc);
 /* Read and optionally reset the accumulated subsweep statistics (synchronises). */
 int pmc_stats_read(pmc_ctx* ctx, pmc_stats* out, int reset);
 /* Device error flags (bit 0: shift overflow, bit 1: assign overflow, bit 2: assign range, bits 3-4:

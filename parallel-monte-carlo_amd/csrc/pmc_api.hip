@@ -14,6 +14,7 @@
 #include "pmc_ctx.h"
 #include "../../include/pmc_pairobs.h"
 #include "../../include/pmc_probe.h"
+#include "../../include/pmc_gc.h"
 #include "../../include/pmc_sk.h"
 
 using namespace pmc;
@@ -22,6 +23,7 @@ using namespace pmc_sched;
 static_assert(kPairObsMaxBins == PMC_PAIROBS_MAX_BINS, "pair observables: bin cap");
 static_assert(kProbeMaxBins == PMC_PROBE_MAX_BINS, "test-particle energies: bin cap");
 static_assert(kSkMaxK == PMC_SK_MAX_K, "density modes: vector cap");
+static_assert(kGcCounters == PMC_GC_COUNTERS && sizeof(pmc_gc_stats) == 8 * PMC_GC_COUNTERS, "exchange moves: counters");
 
 int pmc::issue_phases(pmc_ctx* c, hipStream_t st, int* ovf, unsigned long long* stats, int z0, int z1, uint32_t sweep,
                       const pmc_sweep_plan_t& plan, int k0, int k1, PhaseKind kind, float* mirror, int64_t phase0) {
@@ -307,6 +309,7 @@ void pmc_destroy(pmc_ctx* c) {
     if (c->pobs) (void)hipFree(c->pobs);
     if (c->probe_acc) (void)hipFree(c->probe_acc);
     if (c->sk_acc) (void)hipFree(c->sk_acc);
+    if (c->gc_acc) (void)hipFree(c->gc_acc);
     if (c->flags) (void)hipFree(c->flags);
     if (c->ovf) (void)hipFree(c->ovf);
     if (c->ovf_aux) (void)hipFree(c->ovf_aux);
@@ -782,6 +785,100 @@ int pmc_density_modes(pmc_ctx* c, const int32_t* h_hkl, int nk, int64_t* h_re, i
     return PMC_OK;
 }
 
+// ---- grand-canonical exchange moves (pmc_gc.h) --------------------------------------------------
+namespace {
+
+// the checks every exchange call shares; tab: pmc_gc_table's a[n]
+int gc_args(const pmc_ctx* c, const char* fn, float activity, int k_per_cell, float tab[64]) {
+    const std::string f(fn);
+    if (k_per_cell < 1 || k_per_cell > PMC_GC_MAX_K) return fail(PMC_ERR_ARG, f + ": k_per_cell must be in 1..64");
+    if (c->P.halo == 2) return fail(PMC_ERR_ARG, f + ": two-plane halos are not supported (halo must be 0 or 1)");
+    if (c->P.flags & (PMC_FLAG_QUIRK_R1 | PMC_FLAG_QUIRK_R2))
+        return fail(PMC_ERR_ARG, f + ": the R1 / R2 quirk flags are not supported");
+    if (!std::isfinite(activity) || !(activity > 0.0f) || pmc_gc_table(activity, c->P.w, c->P.nmax, tab))
+        return fail(PMC_ERR_ARG, f + ": the activity must be finite and > 0, with z * w^3 / (n + 1) a positive normal "
+                                     "float for every n < nmax");
+    return PMC_OK;
+}
+
+int gc_read(pmc_ctx* c, pmc_gc_stats* out) {
+    std::memset(out, 0, sizeof(*out));
+    if (!c->gc_acc) return PMC_OK;
+    unsigned long long h[kGcCopies * kGcCounters];
+    PMC_HIP(hipMemcpyAsync(h, c->gc_acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    unsigned long long s[kGcCounters] = {};
+    for (int k = 0; k < kGcCopies; ++k)
+        for (int i = 0; i < kGcCounters; ++i) s[i] += h[k * kGcCounters + i];
+    int64_t* o = &out->ins_trials;   // nine int64 fields in the counters' order (static_assert above)
+    for (int i = 0; i < kGcCounters; ++i) o[i] = (int64_t)s[i];
+    return PMC_OK;
+}
+
+}  // namespace
+
+int pmc_exchange_phase(pmc_ctx* c, int colour, uint32_t sweep, float activity, int k_per_cell) {
+    if (!c) return fail(PMC_ERR_ARG, "null ctx");
+    if (colour < 0 || colour > 7) return fail(PMC_ERR_ARG, "pmc_exchange_phase: colour must be in 0..7");
+    float tab[64];
+    if (int rc = gc_args(c, "pmc_exchange_phase", activity, k_per_cell, tab)) return rc;
+    // the kernel reads both halos, as the energy does (energy_fixed)
+    if (slab_pending_zdir(c))
+        return fail(PMC_ERR_ARG, "pmc_exchange_phase: a slab halo exchange is pending (call pmc_slab_finish first)");
+    if (int rj = slab_join(c)) return rj;
+    if (!c->gc_acc) {
+        PMC_HIP(hipMalloc(&c->gc_acc, sizeof(unsigned long long) * kGcCopies * kGcCounters));
+        PMC_HIP(hipMemsetAsync(c->gc_acc, 0, sizeof(unsigned long long) * kGcCopies * kGcCounters, c->stream));
+    }
+    int o[3];
+    pmc_colour_offset(colour, o);
+    hipError_t e = launch_exchange(c->G, c->disk[c->cur], c->n[c->cur], c->gc_acc, o[0], o[1], o[2], sweep, tab,
+                                   k_per_cell, c->stream);
+    return e == hipSuccess ? PMC_OK : hip_fail(e, "exchange launch");
+}
+
+int pmc_exchange_sweep(pmc_ctx* c, uint32_t sweep, float activity, int k_per_cell) {
+    if (!c) return fail(PMC_ERR_ARG, "null ctx");
+    float tab[64];
+    if (int rc = gc_args(c, "pmc_exchange_sweep", activity, k_per_cell, tab)) return rc;
+    if (c->P.halo && !c->slab)
+        return fail(PMC_ERR_ARG, "pmc_exchange_sweep: a slab context needs the slab driver (pmc_slab_init); without it "
+                                 "run pmc_exchange_phase and refresh the halos after every phase");
+    if (c->slab)   // collective: a deferred z exchange goes out first
+        if (int rc = pmc_slab_finish(c)) return rc;
+    const pmc_sweep_plan_t plan = pmc_plan_for_sweep_ex(c->P.seed, sweep, c->P.w, c->P.flags);
+    for (int k = 0; k < 8; ++k) {
+        if (int rc = pmc_exchange_phase(c, plan.order[k], sweep, activity, k_per_cell)) return rc;
+        if (c->slab)   // the phase changed boundary planes another rank holds as halos
+            if (int rc = pmc_slab_exchange(c)) return rc;
+    }
+    return PMC_OK;
+}
+
+int pmc_gc_stats_read(pmc_ctx* c, pmc_gc_stats* out, int reset) {
+    if (!c || !out) return fail(PMC_ERR_ARG, "bad argument");
+    if (int rj = slab_join(c)) return rj;
+    if (int rc = gc_read(c, out)) return rc;
+    if (reset && c->gc_acc) {
+        PMC_HIP(hipMemsetAsync(c->gc_acc, 0, sizeof(unsigned long long) * kGcCopies * kGcCounters, c->stream));
+        PMC_HIP(hipStreamSynchronize(c->stream));
+    }
+    return PMC_OK;
+}
+
+int pmc_particle_count(pmc_ctx* c, int64_t* n) {
+    if (!c || !n) return fail(PMC_ERR_ARG, "bad argument");
+    if (int rj = slab_join(c)) return rj;
+    // the owned planes' counts are one contiguous run of the storage
+    std::vector<int16_t> h(plane_cells(c) * (size_t)c->P.nz_local);
+    PMC_HIP(hipMemcpyAsync(h.data(), n_plane(c, 0), sizeof(int16_t) * h.size(), hipMemcpyDeviceToHost, c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    int64_t s = 0;
+    for (int16_t v : h) s += v < 0 ? 0 : (v > c->P.nmax ? c->P.nmax : v);
+    *n = s;
+    return PMC_OK;
+}
+
 int pmc_stats_read(pmc_ctx* c, pmc_stats* out, int reset) {
     if (!c || !out) return fail(PMC_ERR_ARG, "bad argument");
     if (int rj = slab_join(c)) return rj;
@@ -906,6 +1003,47 @@ int pmc_start_ex(pmc_ctx* c, uint32_t first, int mc_passes, int flags, pmc_resul
 
 int pmc_start(pmc_ctx* c, uint32_t first, int mc_passes, pmc_result* out) {
     return pmc_start_ex(c, first, mc_passes, 0, out);
+}
+
+int pmc_start_gc(pmc_ctx* c, uint32_t first, int mc_passes, int gc_every, float activity, int k_per_cell,
+                 pmc_result* out, pmc_gc_stats* gc) {
+    if (!c || mc_passes < 0) return fail(PMC_ERR_ARG, "bad argument");
+    if (gc_every < 1) return fail(PMC_ERR_ARG, "pmc_start_gc: gc_every must be >= 1");
+    if (c->P.halo) return fail(PMC_ERR_ARG, "pmc_start_gc drives the whole box");
+    float tab[64];
+    int rc = gc_args(c, "pmc_start_gc", activity, k_per_cell, tab);
+    if (rc) return rc;
+    pmc_result r;
+    std::memset(&r, 0, sizeof(r));
+    pmc_stats s0, s1;
+    pmc_gc_stats g0, g1;
+    if ((rc = pmc_stats_read(c, &s0, 0)) || (rc = gc_read(c, &g0)) || (rc = pmc_energy(c, &r.e_initial))) return rc;
+    PMC_HIP(hipEventRecord(c->ev0, c->stream));
+    for (int k = 0; k < mc_passes; ++k) {
+        const uint32_t s = first + (uint32_t)k;
+        if ((rc = enqueue_sweep(c, s))) return rc;
+        if ((s + 1u) % (uint32_t)gc_every == 0u && (rc = pmc_exchange_sweep(c, s, activity, k_per_cell))) return rc;
+    }
+    PMC_HIP(hipEventRecord(c->ev1, c->stream));
+    PMC_HIP(hipEventSynchronize(c->ev1));
+    float ms = 0.0f;
+    PMC_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    r.seconds = ms * 1e-3;
+    if ((rc = pmc_energy(c, &r.e_final)) || (rc = pmc_stats_read(c, &s1, 0)) || (rc = gc_read(c, &g1))) return rc;
+    r.stats.de_fixed = s1.de_fixed - s0.de_fixed;
+    r.stats.accepted = s1.accepted - s0.accepted;
+    r.stats.trials = s1.trials - s0.trials;
+    r.stats.evaluated = s1.evaluated - s0.evaluated;
+    r.sweeps = mc_passes;
+    const int64_t *a = &g0.ins_trials, *b = &g1.ins_trials;
+    int64_t* d = &g1.ins_trials;
+    for (int i = 0; i < kGcCounters; ++i) d[i] = b[i] - a[i];
+    uint32_t fl = 0;
+    if ((rc = pmc_error_flags(c, &fl, 0))) return rc;
+    if (out) *out = r;
+    if (gc) *gc = g1;
+    if (fl & 1u) return fail(PMC_ERR_OVERFLOW, "shiftCells: cell occupancy exceeded nmax");
+    return PMC_OK;
 }
 
 int pmc_copy_out(pmc_ctx* c, float* h_disk, int16_t* h_n) {

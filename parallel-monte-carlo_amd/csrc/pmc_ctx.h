@@ -30,6 +30,7 @@ struct pmc_ctx {
     unsigned long long* probe_acc = nullptr;   // test-particle energies: accumulator copies (allocated on first use)
     unsigned long long* sk_acc = nullptr;      // density modes: accumulator copies, then the vectors (grown with nk)
     int sk_cap = 0;                            // vectors sk_acc has room for
+    unsigned long long* gc_acc = nullptr;      // exchange moves: accumulator copies (allocated on first use; kept until reset)
     uint32_t* flags = nullptr;
     int* ovf = nullptr;                   // subsweep overflow queue (1 + cells per colour)
     int* ovf_aux = nullptr;                // second queue: launches on a caller stream (pmc_phase_range_on)

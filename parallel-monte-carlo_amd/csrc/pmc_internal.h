@@ -175,6 +175,14 @@ constexpr int kProbeMaxBins = 512;   // PMC_PROBE_MAX_BINS
 static_assert((kProbeCopies & (kProbeCopies - 1)) == 0, "accumulator copies: a power of two");
 hipError_t launch_probe(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int mode,
                         int k_per_cell, uint32_t sample, int64_t lo4, int64_t bw4, int nbins, hipStream_t st);
+// grand-canonical exchange moves (k_exchange, pmc_gc.h): one colour phase, in place.  acc holds
+// kGcCopies accumulator copies of the kGcCounters counters of pmc_gc_stats (in its order), accumulated
+// across launches; the host sums the copies.  table: pmc_gc_table's nmax entries (HOST memory)
+constexpr int kGcCopies = 32;
+constexpr int kGcCounters = 9;   // PMC_GC_COUNTERS
+static_assert((kGcCopies & (kGcCopies - 1)) == 0, "accumulator copies: a power of two");
+hipError_t launch_exchange(const DevGeom& g, float* disk, int16_t* n, unsigned long long* acc, int ox, int oy, int oz,
+                           uint32_t sweep, const float* table, int k_per_cell, hipStream_t st);
 // density modes (k_sk, pmc_sk.h): acc holds kSkCopies accumulator copies of kSkHead + 2 * nk counters
 // each ([0] owned particles, then re[nk], then im[nk]), zeroed on st before the call; the host sums the
 // copies.  hkl: nk (h_x, h_y, h_z) triples in DEVICE memory

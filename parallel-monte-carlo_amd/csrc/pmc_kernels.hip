@@ -27,6 +27,7 @@
 #include "../../include/pmc_detmath.h"
 #include "../../include/pmc_pairobs.h"
 #include "../../include/pmc_probe.h"
+#include "../../include/pmc_gc.h"
 #include "../../include/pmc_sk.h"
 
 namespace pmc {
@@ -2996,6 +2997,240 @@ __global__ __launch_bounds__(kWave) void k_probe(DevGeom g, const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------
+// grand-canonical exchange moves (include/pmc_gc.h): one colour phase of insertions and deletions.
+// One wave per active cell at a time (a fixed grid of waves strides over the colour's cells): the
+// cell's stencil from pairobs_stencil, then k_probe's staging in two regions of LDS -- the own
+// cell's particles, unshifted and unfiltered, in [0, nmax), a region of their own that grows and
+// shrinks with the accepted moves, and the neighbours' box-filtered partners from nmax on (capacity
+// 27 * nmax in all).  Lane k draws attempt k's Philox words, its insert position and its threshold
+// once; the kpc attempts then run as a sequential chain: the 64 lanes take the n own particles and
+// the staged partners in blocks of 64 (a delete skips its own slot), one DPP wave reduction gives
+// E4, and the wave-uniform decision updates the own list in LDS.  After the chain the slots from the
+// lowest one written to the final count, and the count if it changed, go back to memory once.  The
+// nine counters stay wave-uniform and are flushed once per wave with 64-bit atomics into one of
+// kGcCopies accumulator copies.  Equal to tests/gc_ref.c bit for bit.
+// ------------------------------------------------------------------------------------------
+struct GcTable {
+    float a[64];   // pmc_gc_table's a[n] (entries >= nmax unused)
+};
+
+template <int NSLOT, bool OFF32>
+__global__ __launch_bounds__(kWave) void k_exchange(DevGeom g, float* disk, int16_t* ncnt,
+                                                    unsigned long long* __restrict__ acc, uint32_t active_cells,
+                                                    int ox, int oy, int oz, int kpc, uint32_t sweep, GcTable tab) {
+    extern __shared__ __attribute__((aligned(16))) float psm[];
+    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
+    constexpr int CPP = kWave / HS;    // cells per staging pass
+    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
+    using DA = DiskAddr<OFF32>;
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int cap = 27 * nm;
+    float* ex_ = psm;
+    float* ey_ = psm + cap;
+    float* ez_ = psm + 2 * cap;
+    int* inv_l = (int*)(psm + 3 * cap);            // list entry -> stencil lane (32 ints)
+    const int p = lane % HS;
+    const int ee = lane / HS;
+    const float rc2 = g.rc2;
+    const float a_l = tab.a[lane];                 // lane n holds a[n]
+    long long c_it = 0, c_ia = 0, c_if = 0, c_dt = 0, c_da = 0, c_de = 0, c_hard = 0, c_e = 0;   // wave-uniform
+    if (lane < 32) inv_l[lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+
+    const uint32_t ncx = (uint32_t)(g.cps_x / 2), ncy = (uint32_t)(g.cps_y / 2);
+    for (uint32_t a = blockIdx.x; a < active_cells; a += gridDim.x) {
+        // ---- the a-th cell of the colour: (2 ta + ox, 2 tb + oy, local plane 2 tc + oz); z0 is even
+        const uint32_t q1 = udiv_magic(a, g.div_ncx);
+        const uint32_t tc = udiv_magic(q1, g.div_ncy);
+        const uint32_t cxu = 2u * (a - q1 * ncx) + (uint32_t)ox, cyu = 2u * (q1 - tc * ncy) + (uint32_t)oy;
+        const uint32_t zl = 2u * tc + (uint32_t)oz;
+        const PairObsStencil cur = pairobs_stencil(g, ncnt, cxu + (uint32_t)g.cps_x * (cyu + (uint32_t)g.cps_y * zl));
+        const int cx = __builtin_amdgcn_readfirstlane(cur.x), cy = __builtin_amdgcn_readfirstlane(cur.y);
+        const int czg = __builtin_amdgcn_readfirstlane(cur.zg);
+        const int n0 = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
+        const uint32_t own_off = (uint32_t)__builtin_amdgcn_readfirstlane(cur.kc) * (uint32_t)(3 * nm);
+
+        // ---- stage.  Own cell: slots [0, n0) as stored (no image shift, no filter) into [0, n0)
+        if (lane < n0) {
+            float ux, uy, uz;
+            DA::ld3(disk, (own_off + (uint32_t)lane * lay_slot()) * DA::kUnit, lay_dim(nm), ux, uy, uz);
+            ex_[lane] = ux;
+            ey_[lane] = uy;
+            ez_[lane] = uz;
+        }
+        // neighbours (k_probe's staging over stencil cells 1..26): rows of slots [0, HS) of the occupied
+        // cells, then the fuller cells' slots [HS, n) in chunks, through the pmc_box_d2 filter, from nm on
+        float blo[3], bhi[3];
+        pmc_cell_box(cx, cy, czg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
+        auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
+        int S = nm;
+        auto put = [&](bool act, float ux, float uy, float uz) {
+            const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+            if (act) {
+                const int dst = S + mbcnt64(am);
+                ex_[dst] = ux;
+                ey_[dst] = uy;
+                ez_[dst] = uz;
+            }
+            S += __popcll(am);
+        };
+        {
+            const unsigned long long mo = __builtin_amdgcn_ballot_w64(cur.cnt > 0 && lane > 0);
+            const int ncells = __popcll(mo);
+            if (cur.cnt > 0 && lane > 0) inv_l[mbcnt64(mo)] = lane;
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+            for (int q = 0; q < NPMAX; ++q) {
+                const int e = q * CPP + ee;
+                const int src = inv_l[e < ncells ? e : 0];
+                const int c_cnt = __shfl(cur.cnt, src);
+                const int c_idx = __shfl(cur.kc, src);
+                const float isx = __shfl(cur.sx, src), isy = __shfl(cur.sy, src), isz = __shfl(cur.sz, src);
+                const bool act = e < ncells && p < c_cnt;
+                float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+                if (act) {
+                    const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
+                    DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+                    ux = ux + isx;   // (+0 for the cells that are not wrapped)
+                    uy = uy + isy;
+                    uz = uz + isz;
+                }
+                if (q * CPP < ncells) put(act && near(ux, uy, uz), ux, uy, uz);
+            }
+            if constexpr (NSLOT > HS) {
+                for (int s0 = HS; s0 < nm; s0 += HS) {
+                    unsigned long long ov = __builtin_amdgcn_ballot_w64(lane > 0 && cur.cnt > s0);
+                    while (ov) {
+                        int ks = 0, nc = 0;
+                        for (; nc < CPP && ov; ++nc) {
+                            const int kb = (int)__builtin_ctzll(ov);
+                            ov &= ov - 1ull;
+                            ks = ee == nc ? kb : ks;
+                        }
+                        const int c_cnt = __shfl(cur.cnt, ks);
+                        const int c_idx = __shfl(cur.kc, ks);
+                        const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
+                        const int ps = s0 + p;
+                        const bool act = ee < nc && ps < c_cnt;
+                        float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+                        if (act) {
+                            const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
+                            DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+                            ux = ux + isx;
+                            uy = uy + isy;
+                            uz = uz + isz;
+                        }
+                        put(act && near(ux, uy, uz), ux, uy, uz);
+                    }
+                }
+            }
+        }
+        const int snb = S - nm;   // staged partners of the neighbours: [nm, nm + snb), snb <= 26 * nm
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+
+        // ---- lane k: attempt k's words, insert position and threshold
+        const uint32_t gid = (uint32_t)cx + (uint32_t)g.cps_x * ((uint32_t)cy + (uint32_t)g.cps_y * (uint32_t)czg);
+        const pmc_u32x4 wa = philox_rare((uint32_t)lane, gid, sweep, PMC_TAG_GC, g);
+        const pmc_u32x4 wb = philox_rare((uint32_t)lane, gid, sweep, PMC_TAG_GC_ACCEPT, g);
+        const float px = pmc_probe_coord(wa.v[0], cx, g.w, g.Lx);
+        const float py = pmc_probe_coord(wa.v[1], cy, g.w, g.Ly);
+        const float pz = pmc_probe_coord(wa.v[2], czg, g.w, g.Lz);
+        const float thr = pmc_accept_threshold(wb);
+
+        // ---- the chain
+        int n = n0, lo = nm;   // lo: the lowest own slot written so far
+        for (int k = 0; k < kpc; ++k) {
+            const bool del = ((uint32_t)__builtin_amdgcn_readlane((int)wa.v[3], k) >> 31) != 0u;
+            float xi, yi, zi;
+            int skip = -1;
+            if (!del) {
+                ++c_it;
+                if (n == nm) {
+                    ++c_if;
+                    continue;
+                }
+                xi = as_f(__builtin_amdgcn_readlane(as_i(px), k));
+                yi = as_f(__builtin_amdgcn_readlane(as_i(py), k));
+                zi = as_f(__builtin_amdgcn_readlane(as_i(pz), k));
+            } else {
+                ++c_dt;
+                if (n == 0) {
+                    ++c_de;
+                    continue;
+                }
+                skip = (int)pmc_bounded((uint32_t)__builtin_amdgcn_readlane((int)wa.v[0], k), (uint32_t)n);
+                xi = ex_[skip];
+                yi = ey_[skip];
+                zi = ez_[skip];
+            }
+            const int total = n + snb;   // own [0, n), then the neighbours' partners
+            long long sum = 0;                 // per lane
+            unsigned long long hard = 0;       // lanes with a partner inside the core
+            for (int jb = 0; jb < total; jb += kWave) {
+                const int j = jb + lane;
+                const bool vj = j < total && j != skip;
+                const int jj = j < total ? (j < n ? j : j - n + nm) : 0;
+                const float r2 = pmc_r2(xi - ex_[jj], yi - ey_[jj], zi - ez_[jj]);
+                const bool in = vj && r2 <= rc2;
+                if (__builtin_amdgcn_ballot_w64(in) == 0ull) continue;
+                const bool core = in && r2 < PMC_PROBE_CORE_R2;
+                hard |= __builtin_amdgcn_ballot_w64(core);
+                const long long t = pmc_to_fixed_f32(pmc_lj4_from_r2(r2, rc2));
+                sum += in && !core ? t : 0ll;
+            }
+            const long long e4 = wave_sum_i64(sum);
+            const float tk = as_f(__builtin_amdgcn_readlane(as_i(thr), k));
+            bool accept;
+            if (!del) {
+                const float an = as_f(__builtin_amdgcn_readlane(as_i(a_l), n));
+                accept = hard == 0ull && pmc_gc_accept_insert(g.beta, e4, an, tk) != 0;
+            } else {
+                const float an1 = as_f(__builtin_amdgcn_readlane(as_i(a_l), n - 1));
+                accept = hard != 0ull || pmc_gc_accept_delete(g.beta, e4, an1, tk) != 0;
+            }
+            accept = __builtin_amdgcn_readfirstlane((int)accept) != 0;
+            if (hard) ++c_hard;
+            if (!accept) continue;
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            if (!del) {
+                if (lane == 0) {
+                    ex_[n] = xi;
+                    ey_[n] = yi;
+                    ez_[n] = zi;
+                }
+                lo = n < lo ? n : lo;
+                ++n;
+                ++c_ia;
+                c_e += 4 * e4;
+            } else {
+                if (lane == 0) {   // slot i takes slot n-1's coordinates (i == n-1: itself)
+                    ex_[skip] = ex_[n - 1];
+                    ey_[skip] = ey_[n - 1];
+                    ez_[skip] = ez_[n - 1];
+                }
+                lo = skip < lo ? skip : lo;
+                --n;
+                ++c_da;
+                c_e -= 4 * e4;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        }
+
+        // ---- write back: the own slots [lo, n) and the count
+        if (lane >= lo && lane < n)
+            DA::st3(disk, (own_off + (uint32_t)lane * lay_slot()) * DA::kUnit, lay_dim(nm), ex_[lane], ey_[lane], ez_[lane]);
+        if (lane == 0 && n != n0) ncnt[own_off / (uint32_t)(3 * nm)] = (int16_t)n;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+    }
+    // ---- flush: the wave's nine counters (pmc_gc_stats' order)
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kGcCopies - 1)) * (size_t)kGcCounters;
+    const long long v = lane == 0 ? c_it : lane == 1 ? c_ia : lane == 2 ? c_if : lane == 3 ? c_dt : lane == 4 ? c_da
+                        : lane == 5 ? c_de : lane == 6 ? c_hard : lane == 7 ? c_e : c_ia - c_da;
+    if (lane < kGcCounters && v != 0) atomicAdd(&mine[lane], (unsigned long long)v);
+}
+
+// ------------------------------------------------------------------------------------------
 // density modes (include/pmc_sk.h): rho(k) = sum_j exp(i k.r_j) over the owned cells' particles for
 // nk reciprocal-lattice vectors.  The other way round from every kernel above: the LANES are wave
 // vectors (blockIdx.y: blocks of 64), the particles are wave-uniform, and there is no stencil.  A
@@ -3960,6 +4195,28 @@ hipError_t launch_probe(const DevGeom& g, const float* disk, const int16_t* n, u
         constexpr bool O = decltype(off)::value;
         hipLaunchKernelGGL((k_probe<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, mode, k_per_cell,
                            sample, (long long)lo4, (long long)bw4, inv_bw, nbins);
+    });
+    return hipGetLastError();
+}
+
+// acc: kGcCopies copies of pmc_gc_stats' nine counters, accumulated across launches (the host zeroes
+// them on a reset).  A fixed grid of at most 8192 waves over the colour's owned cells: 5.2 KiB of LDS
+// per wave at nmax 16, so 30 waves per CU are resident and the sequential chains hide each other's
+// latency.
+hipError_t launch_exchange(const DevGeom& g, float* disk, int16_t* n, unsigned long long* acc, int ox, int oy, int oz,
+                           uint32_t sweep, const float* table, int k_per_cell, hipStream_t st) {
+    if (k_per_cell < 1 || k_per_cell > PMC_GC_MAX_K || g.halo > 1 || ((ox | oy | oz) & ~1)) return hipErrorInvalidValue;
+    const int64_t active = (int64_t)(g.cps_x / 2) * (g.cps_y / 2) * (g.nz_local / 2);
+    const dim3 grid((unsigned)(active < 8192 ? active : 8192)), block(kWave);
+    const size_t lds = sizeof(float) * (3 * 27 * (size_t)g.nmax + 32);
+    GcTable tab;
+    for (int i = 0; i < 64; ++i) tab.a[i] = i < g.nmax ? table[i] : 0.0f;
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_probe
+    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
+        hipLaunchKernelGGL((k_exchange<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)active, ox, oy, oz,
+                           k_per_cell, sweep, tab);
     });
     return hipGetLastError();
 }

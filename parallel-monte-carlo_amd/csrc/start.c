@@ -5,7 +5,7 @@
  *   start [--cps 4] [--atoms 64] [--passes 1000] [--nmax 16] [--moves 10] [--beta 0.3]
  *         [--sigma 0.5] [--w 2.5] [--seed 1234] [--every 1] [--graph]
  *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS] [--widom K]
- *         [--sk HMAX]
+ *         [--sk HMAX] [--gcmc Z [--gc-moves K] [--gc-every M]]
  *
  * --dump writes create_dump frames (kernel.cu:510-536; the reference's VISUALISATION path) of the
  * initial state and after every --every sweeps; --save writes a PMCSNAP1 snapshot at the end;
@@ -20,6 +20,11 @@
  * --sk HMAX (<= 1024) evaluates the density modes of the final state (pmc_density_modes) at (h,0,0),
  * (0,h,0), (0,0,h) for h = 1..HMAX and prints one `sk` line per h with |k| = 2 pi h / L and the mean
  * of the three S(k) = |rho(k)|^2 / N, then a closing `structure` line with N.
+ *
+ * --gcmc Z samples the grand-canonical ensemble at activity Z = exp(beta mu) / Lambda^3 (pmc_start_gc):
+ * after every sweep s with (s + 1) % M == 0 (--gc-every, default 1) one exchange sweep of K insert /
+ * delete attempts per cell and colour phase (--gc-moves, default 1).  Every report line then also
+ * prints the particle number N and the interval's insert and delete acceptance; not with --graph.
  *
  * Prints "step: energy" lines like kernel.cu:643,695 (energy from the cell-list sum every
  * --every sweeps) and a final summary with acceptance ratio and trial-moves/s.  Compile-time
@@ -43,7 +48,8 @@ int main(int argc, char** argv) {
     p.cps_x = 4; p.nmax = 16; p.n_moves = 10;
     p.w = 2.5f; p.beta = 0.3f; p.sigma = 0.5f; p.seed = 1234;
     long long atoms = 64;
-    int passes = 1000, every = 1, graph = 0, pairobs = 0, widom = 0, sk = 0;
+    int passes = 1000, every = 1, graph = 0, pairobs = 0, widom = 0, sk = 0, gc_moves = 1, gc_every = 1;
+    float gcmc = 0.0f;
     const char *dump = NULL, *save = NULL, *restart = NULL;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -65,10 +71,14 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--pairobs")) { pairobs = atoi(v); ++i; }
         else if (!strcmp(a, "--widom")) { widom = atoi(v); ++i; }
         else if (!strcmp(a, "--sk")) { sk = atoi(v); ++i; }
+        else if (!strcmp(a, "--gcmc")) { gcmc = (float)atof(v); ++i; }
+        else if (!strcmp(a, "--gc-moves")) { gc_moves = atoi(v); ++i; }
+        else if (!strcmp(a, "--gc-every")) { gc_every = atoi(v); ++i; }
         else { fprintf(stderr, "unknown flag %s\n", a); return 2; }
     }
     if (every < 1) every = 1;
     if (sk < 0 || sk > 1024) { fprintf(stderr, "--sk HMAX: 1..1024\n"); return 2; }
+    if (gcmc != 0.0f && graph) { fprintf(stderr, "--gcmc cannot be combined with --graph\n"); return 2; }
 
     pmc_ctx* ctx = NULL;
     int rc = pmc_create(&p, &ctx);
@@ -103,6 +113,20 @@ int main(int argc, char** argv) {
             total.trials += b.trials - a.trials;
             total.evaluated += b.evaluated - a.evaluated;
             total.de_fixed += b.de_fixed - a.de_fixed;
+        } else if (gcmc != 0.0f) {
+            pmc_gc_stats g;
+            int64_t n_now = 0;
+            if ((rc = pmc_start_gc(ctx, s, k, gc_every, gcmc, gc_moves, &r, &g))) die("pmc_start_gc", rc);
+            if ((rc = pmc_particle_count(ctx, &n_now))) die("pmc_particle_count", rc);
+            e = r.e_final;
+            seconds += r.seconds;
+            total.accepted += r.stats.accepted;
+            total.trials += r.stats.trials;
+            total.evaluated += r.stats.evaluated;
+            total.de_fixed += r.stats.de_fixed;
+            printf("%u: %f N %lld insert %.6f delete %.6f\n", (unsigned)(s + (uint32_t)k), e, (long long)n_now,
+                   g.ins_trials ? (double)g.ins_accepted / (double)g.ins_trials : 0.0,
+                   g.del_trials ? (double)g.del_accepted / (double)g.del_trials : 0.0);
         } else {
             /* energies once per interval (for the trace line), not around every pmc_start */
             if ((rc = pmc_start_ex(ctx, s, k, PMC_START_NO_ENERGY, &r))) die("pmc_start_ex", rc);
@@ -113,7 +137,7 @@ int main(int argc, char** argv) {
             total.evaluated += r.stats.evaluated;
             total.de_fixed += r.stats.de_fixed;
         }
-        printf("%u: %f\n", (unsigned)(s + (uint32_t)k), e);
+        if (gcmc == 0.0f) printf("%u: %f\n", (unsigned)(s + (uint32_t)k), e);
         if (dump && (rc = pmc_dump_frame(ctx, dump, 1, (int64_t)(s + (uint32_t)k)))) die("pmc_dump_frame", rc);
     }
     if (save && (rc = pmc_save_snapshot(ctx, save, first + (uint32_t)passes))) die("pmc_save_snapshot", rc);

@@ -57,6 +57,16 @@ class SkObs(C.Structure):
     _fields_ = [("particles", C.c_int64)]
 
 
+class GcStats(C.Structure):
+    """``pmc_gc_stats``."""
+
+    _fields_ = [(k, C.c_int64) for k in ("ins_trials", "ins_accepted", "ins_full", "del_trials", "del_accepted",
+                                         "del_empty", "hard", "de_fixed", "dn")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class Result(C.Structure):
     """``pmc_result``."""
 
@@ -170,6 +180,11 @@ def lib():
         _sig(L, "pmc_probe_energies", i32, _vp, i32, i32, u32, C.c_float, C.c_float, i32, _vp, _vp,
              C.POINTER(ProbeObs))
         _sig(L, "pmc_density_modes", i32, _vp, _vp, i32, _vp, _vp, C.POINTER(SkObs))
+        _sig(L, "pmc_exchange_phase", i32, _vp, i32, u32, C.c_float, i32)
+        _sig(L, "pmc_exchange_sweep", i32, _vp, u32, C.c_float, i32)
+        _sig(L, "pmc_gc_stats_read", i32, _vp, C.POINTER(GcStats), i32)
+        _sig(L, "pmc_particle_count", i32, _vp, C.POINTER(i64))
+        _sig(L, "pmc_start_gc", i32, _vp, u32, i32, i32, C.c_float, i32, C.POINTER(Result), C.POINTER(GcStats))
         _sig(L, "pmc_stats_read", i32, _vp, C.POINTER(Stats), i32)
         _sig(L, "pmc_error_flags", i32, _vp, C.POINTER(C.c_uint32), i32)
         _sig(L, "pmc_copy_out", i32, _vp, _vp, _vp)

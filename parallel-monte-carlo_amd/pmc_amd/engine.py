@@ -21,8 +21,8 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT, PMC_PROBE_REAL, PairObs, Params, ProbeObs, Result, SkObs,
-                   Stats, check, lib)
+from ._lib import (PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT, PMC_PROBE_REAL, GcStats, PairObs, Params, ProbeObs, Result,
+                   SkObs, Stats, check, lib)
 
 FIX_SCALE = 2.0 ** 32
 
@@ -277,6 +277,40 @@ class PmcContext:
         check("pmc_start", lib().pmc_start(self._h, first, passes, C.byref(r)))
         out = r.stats.as_dict()
         out.update(e_initial=r.e_initial, e_final=r.e_final, seconds=r.seconds, sweeps=int(r.sweeps))
+        return out
+
+    # ---- grand-canonical exchange moves (include/pmc_gc.h) ------------------------------------
+    def exchange_phase(self, colour: int, s: int, z: float, k: int = 1) -> None:
+        """One insert/delete phase of colour 0..7 at activity z = exp(beta mu) / Lambda^3, k attempts per
+        active cell (pmc_exchange_phase).  On a slab context the halos are stale afterwards."""
+        check("pmc_exchange_phase", lib().pmc_exchange_phase(self._h, colour, s & 0xFFFFFFFF, z, k))
+
+    def exchange_sweep(self, s: int, z: float, k: int = 1) -> None:
+        """The 8 colours' exchange phases in sweep s's colour order (pmc_exchange_sweep); collective on
+        a context with the slab driver (a halo exchange after every phase)."""
+        check("pmc_exchange_sweep", lib().pmc_exchange_sweep(self._h, s & 0xFFFFFFFF, z, k))
+
+    def gc_stats(self, reset: bool = False) -> dict:
+        """The accumulated exchange counters (pmc_gc_stats); observables.gc_acceptance converts them."""
+        g = GcStats()
+        check("pmc_gc_stats_read", lib().pmc_gc_stats_read(self._h, C.byref(g), int(reset)))
+        return g.as_dict()
+
+    def particle_count(self) -> int:
+        """Particles in the owned cells (pmc_particle_count)."""
+        n = C.c_int64(0)
+        check("pmc_particle_count", lib().pmc_particle_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def run_gc(self, first: int, passes: int, z: float, k: int = 1, every: int = 1) -> dict:
+        """pmc_start_gc: `passes` sweeps from `first`, an exchange sweep at activity z (k attempts per
+        cell and phase) after every sweep s with (s + 1) % every == 0.  Returns start()'s dict with the
+        run's exchange counters under "gc"."""
+        r, g = Result(), GcStats()
+        check("pmc_start_gc", lib().pmc_start_gc(self._h, first & 0xFFFFFFFF, passes, every, z, k, C.byref(r),
+                                                 C.byref(g)))
+        out = r.stats.as_dict()
+        out.update(e_initial=r.e_initial, e_final=r.e_final, seconds=r.seconds, sweeps=int(r.sweeps), gc=g.as_dict())
         return out
 
     def run_small(self, first: int, count: int) -> None:

@@ -112,6 +112,27 @@ def energy_distribution(res: dict) -> tuple:
     return centres, hist / (max(int(res["probes"]), 1) * width)
 
 
+# ---- grand-canonical exchange moves (PmcContext.exchange_sweep, include/pmc_gc.h) ----------------
+
+def activity(rho: float, beta: float, mu_excess: float) -> float:
+    """The activity z = exp(beta mu) / Lambda^3 at which a fluid of excess chemical potential
+    mu_excess has density rho: mu = ln(rho Lambda^3) / beta + mu_excess, so z = rho exp(beta mu_excess)
+    (z -> rho for the ideal gas).  mu_excess is in energy units: mu_excess() above returns
+    beta * mu_ex, so pass mu_excess(res, beta) / beta."""
+    return float(rho) * float(np.exp(float(beta) * float(mu_excess)))
+
+
+def gc_acceptance(stats: dict) -> dict:
+    """Acceptance ratios of the exchange counters (PmcContext.gc_stats or run_gc()["gc"]): accepted
+    inserts / insert attempts and accepted deletes / delete attempts (0.0 when there was none), and
+    the fractions of attempts lost to full and to empty cells."""
+    it, dt = int(stats["ins_trials"]), int(stats["del_trials"])
+    return {"insert": stats["ins_accepted"] / it if it else 0.0,
+            "delete": stats["del_accepted"] / dt if dt else 0.0,
+            "full": stats["ins_full"] / it if it else 0.0,
+            "empty": stats["del_empty"] / dt if dt else 0.0}
+
+
 # ---- density modes and S(k) (PmcContext.density_modes, include/pmc_sk.h) ------------------------
 
 def wave_vectors(h_max: int, half_space: bool = True) -> np.ndarray:
