@@ -396,6 +396,28 @@ typedef struct pmc_sk_obs {
     int64_t particles;  /* particles in owned cells */
 } pmc_sk_obs;
 int pmc_density_modes(pmc_ctx* ctx, const int32_t* h_hkl, int nk, int64_t* h_re, int64_t* h_im, pmc_sk_obs* out);
+/* Axis profiles of the owned cells' particles, defined bit for bit in pmc_profile.h: along box axis
+ * `axis` (0 x, 1 y, 2 z), nbins equal bins from -L/2; bin b of h_count counts the particles whose
+ * position word falls in it, and h_vir[d * nbins + b] (d = 0, 1, 2) is the sum over the ORDERED
+ * pairs (i in bin b, j in i's 27-cell stencil, inside the cutoff) of fixed(v d_d^2 / r^2): the
+ * diagonal pair-virial components in the quarter units of the virial sum, each unordered pair half in
+ * each partner's bin.  From them: the density profile, the pressure-tensor profiles P_N and P_T
+ * (Harasima-type assignment; the local NORMAL profile is not flat through an interface under it), the
+ * box-averaged tensor and the surface tension, which are exact with respect to the contour
+ * (pmc_amd.observables).  The reference has no such observable (its only one is calc_energy,
+ * kernel.cu:452-470).  h_count (nbins counters) and h_vir (3 * nbins sums, 2^-32 units) are HOST
+ * pointers.  out->virial_fixed and out->pairs are the integers pmc_pair_observables returns.
+ * PMC_ERR_ARG for a null pointer, an axis outside 0..2, nbins outside 1..min(4096, 64 * cps_axis)
+ * (cps_z the global count), and for a slab context with a pending deferred z exchange
+ * (pmc_slab_finish first, as for pmc_energy).  Runs on the context stream and synchronises; state,
+ * statistics, error flags and the energy are left unchanged.  No cross-rank reduction: every output
+ * is an integer sum and the bins use global coordinates, so the caller adds the ranks' arrays. */
+typedef struct pmc_profile_obs {
+    int64_t virial_fixed;  /* sum over ordered pairs of fixed(v), 2^-32 units: pmc_pair_obs' */
+    int64_t pairs;         /* ordered pairs with r2 <= rc2 */
+    int64_t particles;     /* particles in owned cells */
+} pmc_profile_obs;
+int pmc_profiles(pmc_ctx* ctx, int axis, int nbins, uint64_t* h_count, int64_t* h_vir, pmc_profile_obs* out);
 /* ---- grand-canonical exchange moves (mu V T) ------------------------------------------------
  * Insertions and deletions as a further kind of colour phase, defined bit for bit in pmc_gc.h: every
  * owned cell of the colour runs k_per_cell (1..64) attempts in order on its own particle list, each

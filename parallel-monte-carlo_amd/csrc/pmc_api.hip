@@ -16,6 +16,7 @@
 #include "../../include/pmc_probe.h"
 #include "../../include/pmc_gc.h"
 #include "../../include/pmc_sk.h"
+#include "../../include/pmc_profile.h"
 
 using namespace pmc;
 using namespace pmc_sched;
@@ -309,6 +310,7 @@ void pmc_destroy(pmc_ctx* c) {
     if (c->pobs) (void)hipFree(c->pobs);
     if (c->probe_acc) (void)hipFree(c->probe_acc);
     if (c->sk_acc) (void)hipFree(c->sk_acc);
+    if (c->prof_acc) (void)hipFree(c->prof_acc);
     if (c->gc_acc) (void)hipFree(c->gc_acc);
     if (c->flags) (void)hipFree(c->flags);
     if (c->ovf) (void)hipFree(c->ovf);
@@ -782,6 +784,45 @@ int pmc_density_modes(pmc_ctx* c, const int32_t* h_hkl, int nk, int64_t* h_re, i
         h_re[m] = (int64_t)s[(size_t)kSkHead + (size_t)m];
         h_im[m] = (int64_t)s[(size_t)kSkHead + (size_t)nk + (size_t)m];
     }
+    return PMC_OK;
+}
+
+int pmc_profiles(pmc_ctx* c, int axis, int nbins, uint64_t* h_count, int64_t* h_vir, pmc_profile_obs* out) {
+    if (!c || !h_count || !h_vir || !out) return fail(PMC_ERR_ARG, "bad argument");
+    if (axis < 0 || axis > 2) return fail(PMC_ERR_ARG, "pmc_profiles: axis must be 0, 1 or 2");
+    const int cps_a = axis == 0 ? c->G.cps_x : (axis == 1 ? c->G.cps_y : c->G.cps_z);
+    if (nbins < 1 || nbins > pmc_profile_max_bins(cps_a))
+        return fail(PMC_ERR_ARG, "pmc_profiles: nbins must be in 1..min(4096, 64 * cells along the axis)");
+    // the kernel reads both halos, as the energy does (energy_fixed)
+    if (slab_pending_zdir(c))
+        return fail(PMC_ERR_ARG, "pmc_profiles: a slab halo exchange is pending (call pmc_slab_finish first)");
+    if (int rj = slab_join(c)) return rj;
+    const size_t per = (size_t)kProfHead + 4 * (size_t)nbins;
+    if (nbins > c->prof_cap) {   // allocated on first use, grown with nbins
+        if (c->prof_acc) {
+            PMC_HIP(hipStreamSynchronize(c->stream));
+            PMC_HIP(hipFree(c->prof_acc));
+            c->prof_acc = nullptr;
+            c->prof_cap = 0;
+        }
+        PMC_HIP(hipMalloc(&c->prof_acc, sizeof(unsigned long long) * kProfCopies * per));
+        c->prof_cap = nbins;
+    }
+    PMC_HIP(hipMemsetAsync(c->prof_acc, 0, sizeof(unsigned long long) * kProfCopies * per, c->stream));
+    hipError_t e = launch_profile(c->G, c->disk[c->cur], c->n[c->cur], c->prof_acc, axis, nbins, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "axis profiles launch");
+    std::vector<unsigned long long> h((size_t)kProfCopies * per);
+    PMC_HIP(hipMemcpyAsync(h.data(), c->prof_acc, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost,
+                           c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    std::vector<unsigned long long> s(per, 0ull);
+    for (int k = 0; k < kProfCopies; ++k)
+        for (size_t i = 0; i < per; ++i) s[i] += h[(size_t)k * per + i];
+    out->virial_fixed = (int64_t)s[0];
+    out->pairs = (int64_t)s[1];
+    out->particles = (int64_t)s[2];
+    for (int b = 0; b < nbins; ++b) h_count[b] = (uint64_t)s[(size_t)kProfHead + (size_t)b];
+    for (size_t b = 0; b < 3 * (size_t)nbins; ++b) h_vir[b] = (int64_t)s[(size_t)kProfHead + (size_t)nbins + b];
     return PMC_OK;
 }
 

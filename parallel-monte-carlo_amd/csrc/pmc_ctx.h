@@ -30,6 +30,8 @@ struct pmc_ctx {
     unsigned long long* probe_acc = nullptr;   // test-particle energies: accumulator copies (allocated on first use)
     unsigned long long* sk_acc = nullptr;      // density modes: accumulator copies, then the vectors (grown with nk)
     int sk_cap = 0;                            // vectors sk_acc has room for
+    unsigned long long* prof_acc = nullptr;    // axis profiles: accumulator copies (grown with nbins)
+    int prof_cap = 0;                          // bins prof_acc has room for
     unsigned long long* gc_acc = nullptr;      // exchange moves: accumulator copies (allocated on first use; kept until reset)
     uint32_t* flags = nullptr;
     int* ovf = nullptr;                   // subsweep overflow queue (1 + cells per colour)

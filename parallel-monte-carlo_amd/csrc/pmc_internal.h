@@ -193,6 +193,17 @@ constexpr int kSkRun = 8;       // consecutive owned cells per wave and stride s
 static_assert((kSkCopies & (kSkCopies - 1)) == 0, "accumulator copies: a power of two");
 hipError_t launch_sk(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, const int* hkl,
                      int nk, hipStream_t st);
+// axis profiles (k_profile, pmc_profile.h): acc holds kProfCopies accumulator copies of
+// kProfHead + 4 * nbins counters each ([0] virial sum, [1] ordered pairs in the cutoff, [2] owned
+// particles, then count[nbins], then vir[3][nbins]), zeroed on st before the call; the host sums the
+// copies.  axis 0..2, nbins in 1..pmc_profile_max_bins(cps_axis)
+constexpr int kProfCopies = 32;
+constexpr int kProfHead = 3;
+constexpr int kProfMaxBins = 4096;   // PMC_PROFILE_MAX_BINS
+constexpr int kProfWin = 96;         // bins of a wave's LDS window (a cell touches at most 68)
+static_assert((kProfCopies & (kProfCopies - 1)) == 0, "accumulator copies: a power of two");
+hipError_t launch_profile(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int axis,
+                          int nbins, hipStream_t st);
 // the cells of one colour of one plane: mode 0 plane -> packed buffer, 1 packed -> plane,
 // 2 plane -> plane; (cps_x/2)*(cps_y/2)*3*nmax floats
 hipError_t launch_colour_rows(const DevGeom& g, const float* src, float* dst, int colour, int mode, hipStream_t st);

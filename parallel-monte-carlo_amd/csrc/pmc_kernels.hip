@@ -29,6 +29,7 @@
 #include "../../include/pmc_probe.h"
 #include "../../include/pmc_gc.h"
 #include "../../include/pmc_sk.h"
+#include "../../include/pmc_profile.h"
 
 namespace pmc {
 
@@ -3231,6 +3232,264 @@ __global__ __launch_bounds__(kWave) void k_exchange(DevGeom g, float* disk, int1
 }
 
 // ------------------------------------------------------------------------------------------
+// axis profiles (include/pmc_profile.h): per bin along one box axis, the particle count and the
+// three diagonal pair-virial components over ORDERED pairs, each pair in its own particle's bin.
+// k_pairobs' per-cell form: the same stencil (pairobs_stencil), the same staging (rows of 8 slots,
+// the next cell's while this cell's pairs run, chunks for the fuller cells, own cell first, the
+// pmc_box_d2 filter, 27 * nmax LDS capacity), the same fixed grid of waves over runs of kPairObsRun
+// cells.  The pair loop is the other way round: the OWN particle is the outer loop (readlane), the
+// lanes take its staged partners in blocks of 64 (blocks 0 and 1 from registers, further ones from
+// LDS), every in-cutoff lane evaluates v and the three t_d and adds their fixed-point values to
+// three per-lane int64 sums; one DPP wave reduction per component (wave_sum_i64) gives the
+// particle's sums, which lane i keeps.  After the cell, lanes < n_own add their particle's count and
+// sums to the wave's WINDOW in LDS: kProfWin consecutive bins from wlo (u32 counts, int64 sums,
+// returnless LDS atomics), re-anchored -- flushed with 64-bit global atomics, nonzero entries only --
+// when a cell's bins [floor(c nbins / cps) - 1, floor((c + 1) nbins / cps) + 1] (<= 68 by the nbins
+// limit) do not fit the current one.  A particle whose bin is outside the window (a coordinate a few
+// ulp outside its cell, the wrapped +L/2 edge) adds straight to the global accumulator.  No per-pair
+// atomics.  The virial total is a per-lane int64 sum, the pair / particle counts are wave-uniform;
+// one flush per wave into one of kProfCopies accumulator copies
+// ([virial, pairs, particles, count[nbins], vir[3][nbins]] each) the host sums.
+// Integer sums only: exact in any order, equal to tests/profile_ref.c bit for bit.
+// ------------------------------------------------------------------------------------------
+template <int NSLOT, bool OFF32>
+__global__ __launch_bounds__(kWave) void k_profile(DevGeom g, const float* __restrict__ disk,
+                                                   const int16_t* __restrict__ ncnt,
+                                                   unsigned long long* __restrict__ acc, uint32_t total_cells,
+                                                   int axis, int nbins, int cps_a, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float psm[];
+    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
+    constexpr int CPP = kWave / HS;    // cells per staging pass
+    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
+    using DA = DiskAddr<OFF32>;
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int cap = 27 * nm;
+    unsigned long long* wvir = (unsigned long long*)psm;        // [3][kProfWin] int64 sums of the window
+    unsigned* wcnt = (unsigned*)(wvir + 3 * kProfWin);          // [kProfWin] counts of the window
+    int* inv_l = (int*)(wcnt + kProfWin);                       // list entry -> stencil lane (32 ints)
+    float* ex_ = (float*)(inv_l + 32);
+    float* ey_ = ex_ + cap;
+    float* ez_ = ex_ + 2 * cap;
+    const int p = lane % HS;
+    const int ee = lane / HS;
+    const float rc2 = g.rc2;
+    long long sum = 0;                             // per lane: the virial total
+    unsigned long long n_pairs = 0, n_part = 0;    // wave-uniform
+    for (int b = lane; b < kProfWin; b += kWave) {
+        wcnt[b] = 0u;
+        wvir[b] = wvir[kProfWin + b] = wvir[2 * kProfWin + b] = 0ull;
+    }
+    if (lane < 32) inv_l[lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kProfCopies - 1)) * ((size_t)kProfHead + 4 * (size_t)nbins);
+    unsigned long long* gcnt = mine + kProfHead;
+    unsigned long long* gvir = gcnt + nbins;       // [3][nbins]
+    int wlo = 0;                                   // first bin of the window (wave-uniform; may be -1)
+    // the window's nonzero entries to the global accumulator, the window zeroed
+    auto flush_window = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        for (int e = lane; e < kProfWin; e += kWave) {
+            const int b = wlo + e;
+            const unsigned cn = wcnt[e];
+            const unsigned long long a0 = wvir[e], a1 = wvir[kProfWin + e], a2 = wvir[2 * kProfWin + e];
+            if (b >= 0 && b < nbins) {   // (entries outside [0, nbins) are never written)
+                if (cn) atomicAdd(&gcnt[b], (unsigned long long)cn);
+                if (a0) atomicAdd(&gvir[b], a0);
+                if (a1) atomicAdd(&gvir[(size_t)nbins + b], a1);
+                if (a2) atomicAdd(&gvir[2 * (size_t)nbins + b], a2);
+            }
+            wcnt[e] = 0u;
+            wvir[e] = wvir[kProfWin + e] = wvir[2 * kProfWin + e] = 0ull;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    };
+
+    // rows of the cell in flight (k_pairobs' issue_rows): slots [0, HS) of its occupied stencil cells
+    // (own cell: entry 0 when occupied), in registers
+    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
+    bool vact[NPMAX];
+    int ncells = 0;
+    auto issue_rows = [&](const PairObsStencil& st) {
+        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
+        ncells = __popcll(mo);
+        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int q = 0; q < NPMAX; ++q) {
+            const int e = q * CPP + ee;
+            const int src = inv_l[e < ncells ? e : 0];
+            const int c_cnt = __shfl(st.cnt, src);
+            const int c_idx = __shfl(st.kc, src);
+            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
+            vact[q] = e < ncells && p < c_cnt;
+            vx[q] = vy[q] = vz[q] = 0.0f;
+            if (vact[q]) {
+                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
+                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
+                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
+                vy[q] = vy[q] + isy;
+                vz[q] = vz[q] + isz;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
+    };
+
+    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
+    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
+        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
+        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
+        issue_rows(cur);
+        PairObsStencil nxt = cur;
+        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
+        for (int c = 0; c < ncl; ++c) {
+            // ---- stage cell c (k_pairobs' staging): own particles first, then the filtered partners
+            float blo[3], bhi[3];
+            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
+            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
+            const int ca = axis == 0 ? cur.x : (axis == 1 ? cur.y : cur.zg);   // the cell along the axis
+            int S = 0;
+            auto put = [&](bool act, float ux, float uy, float uz) {
+                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+                if (act) {
+                    const int dst = S + mbcnt64(am);
+                    ex_[dst] = ux;
+                    ey_[dst] = uy;
+                    ez_[dst] = uz;
+                }
+                S += __popcll(am);
+            };
+            // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles
+            auto chunks = [&](unsigned long long mg, bool filter) {
+                if constexpr (NSLOT > HS) {
+                    for (int s0 = HS; s0 < nm; s0 += HS) {
+                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
+                        while (ov) {
+                            int ks = 0, nc = 0;
+                            for (; nc < CPP && ov; ++nc) {
+                                const int kb = (int)__builtin_ctzll(ov);
+                                ov &= ov - 1ull;
+                                ks = ee == nc ? kb : ks;
+                            }
+                            const int c_cnt = __shfl(cur.cnt, ks);
+                            const int c_idx = __shfl(cur.kc, ks);
+                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
+                            const int ps = s0 + p;
+                            const bool act = ee < nc && ps < c_cnt;
+                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+                            if (act) {
+                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
+                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+                                ux = ux + isx;
+                                uy = uy + isy;
+                                uz = uz + isz;
+                            }
+                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz);
+                        }
+                    }
+                }
+            };
+            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
+            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
+            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0]);             // own slots [0, HS)
+            chunks(1ull, false);                                          // own slots [HS, n)
+#pragma unroll
+            for (int q = 0; q < NPMAX; ++q) {
+                const int e = q * CPP + ee;
+                if (q * CPP < ncells) put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q]);
+            }
+            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            // ---- the next cell's rows go out now and arrive while this cell's pairs run
+            if (c + 1 < ncl) {
+                cur = nxt;
+                issue_rows(cur);
+                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
+            }
+            n_part += (unsigned long long)n_own;
+            if (n_own == 0) continue;
+            // ---- the window holds this cell's bins, or is flushed and re-anchored at them
+            {
+                const int lo_c = (int)(((uint32_t)ca * (uint32_t)nbins) / (uint32_t)cps_a) - 1;
+                const int hi_c = (int)(((uint32_t)(ca + 1) * (uint32_t)nbins) / (uint32_t)cps_a) + 1;
+                if (lo_c < wlo || hi_c >= wlo + kProfWin) {
+                    flush_window();
+                    wlo = lo_c;
+                }
+            }
+            // ---- ordered pairs (i, j): own particle i (staged first: lane i of block 0) by readlane,
+            //      lane j holds staged partner j of the block; j == i skipped
+            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+            const int j1 = kWave + lane < S ? kWave + lane : 0;
+            const float px = ex_[j1], py = ey_[j1], pz = ez_[j1];         // block 1
+            long long mx = 0, my = 0, mz = 0;                             // lane i: particle i's sums
+            for (int i = 0; i < n_own; ++i) {
+                const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+                const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+                const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+                long long ax = 0, ay = 0, az = 0;
+                auto block = [&](int jb, float xj, float yj, float zj, bool self) {
+                    const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
+                    const float r2 = pmc_r2(dx, dy, dz);
+                    const bool in = r2 <= rc2 && jb + lane < S && !self;
+                    const unsigned long long im = __builtin_amdgcn_ballot_w64(in);
+                    if (im == 0ull) return;
+                    n_pairs += (unsigned long long)__popcll(im);
+                    if (in) {
+                        const float v = pmc_virial_term(r2);
+                        const float inv = pmc_recip(__builtin_fmaxf(r2, PMC_R2_MIN));
+                        sum += pmc_to_fixed_f32(v);
+                        ax += pmc_to_fixed_f32(pmc_profile_term_inv(v, dx, inv));
+                        ay += pmc_to_fixed_f32(pmc_profile_term_inv(v, dy, inv));
+                        az += pmc_to_fixed_f32(pmc_profile_term_inv(v, dz, inv));
+                    }
+                };
+                block(0, ox, oy, oz, lane == i);
+                if (S > kWave) block(kWave, px, py, pz, false);
+                for (int jb = 2 * kWave; jb < S; jb += kWave) {
+                    const int jj = jb + lane < S ? jb + lane : 0;
+                    block(jb, ex_[jj], ey_[jj], ez_[jj], false);
+                }
+                const long long tx = wave_sum_i64(ax), ty = wave_sum_i64(ay), tz = wave_sum_i64(az);
+                if (lane == i) {
+                    mx = tx;
+                    my = ty;
+                    mz = tz;
+                }
+            }
+            // ---- lanes < n_own: the particle's bin, its count and sums into the window or, outside
+            //      it, the global accumulator
+            if (lane < n_own) {
+                const float oa = axis == 0 ? ox : (axis == 1 ? oy : oz);
+                const int b = (int)pmc_profile_bin(pmc_sk_word(oa, scale), nbins);
+                const int e = b - wlo;
+                if (e >= 0 && e < kProfWin) {
+                    (void)__hip_atomic_fetch_add(&wcnt[e], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    (void)__hip_atomic_fetch_add(&wvir[e], (unsigned long long)mx, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+                    (void)__hip_atomic_fetch_add(&wvir[kProfWin + e], (unsigned long long)my, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+                    (void)__hip_atomic_fetch_add(&wvir[2 * kProfWin + e], (unsigned long long)mz, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+                } else {
+                    atomicAdd(&gcnt[b], 1ull);
+                    if (mx) atomicAdd(&gvir[b], (unsigned long long)mx);
+                    if (my) atomicAdd(&gvir[(size_t)nbins + b], (unsigned long long)my);
+                    if (mz) atomicAdd(&gvir[2 * (size_t)nbins + b], (unsigned long long)mz);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+        }
+    }
+    // ---- flush: the window, then the wave sums (int64, exact in any order)
+    flush_window();
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    const unsigned long long head3 = lane == 0 ? (unsigned long long)sum : (lane == 1 ? n_pairs : n_part);
+    if (lane < kProfHead && head3 != 0) atomicAdd(&mine[lane], head3);
+}
+
+// ------------------------------------------------------------------------------------------
 // density modes (include/pmc_sk.h): rho(k) = sum_j exp(i k.r_j) over the owned cells' particles for
 // nk reciprocal-lattice vectors.  The other way round from every kernel above: the LANES are wave
 // vectors (blockIdx.y: blocks of 64), the particles are wave-uniform, and there is no stencil.  A
@@ -4242,6 +4501,30 @@ hipError_t launch_sk(const DevGeom& g, const float* disk, const int16_t* n, unsi
         constexpr bool O = decltype(off)::value;
         hipLaunchKernelGGL((k_sk<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, hkl, nk, lgp, scx,
                            scy, scz);
+    });
+    return hipGetLastError();
+}
+
+// acc: kProfCopies copies of [virial, pairs, particles, count[nbins], vir[3][nbins]], zeroed on st before
+// the call.  launch_pairobs' fixed grid; 7.9 KiB of LDS per wave at nmax 16 (the staged partners, 32
+// list entries and the window of kProfWin bins: 28 B each), whatever nbins.  The window's u32 counts
+// hold at most the particles a wave visits, far below 2^32 (launch_pairobs' bound).
+hipError_t launch_profile(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int axis,
+                          int nbins, hipStream_t st) {
+    if (axis < 0 || axis > 2) return hipErrorInvalidValue;
+    const int cps_a = axis == 0 ? g.cps_x : (axis == 1 ? g.cps_y : g.cps_z);
+    if (nbins < 1 || nbins > pmc_profile_max_bins(cps_a) || nbins > kProfMaxBins) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
+    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
+    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
+    const size_t lds = sizeof(float) * (3 * 27 * (size_t)g.nmax + 32) + (size_t)kProfWin * (3 * 8 + 4);
+    const float scale = pmc_sk_scale(axis == 0 ? g.Lx : (axis == 1 ? g.Ly : g.Lz));
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
+    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
+        hipLaunchKernelGGL((k_profile<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, axis, nbins,
+                           cps_a, scale);
     });
     return hipGetLastError();
 }

@@ -5,7 +5,7 @@
  *   start [--cps 4] [--atoms 64] [--passes 1000] [--nmax 16] [--moves 10] [--beta 0.3]
  *         [--sigma 0.5] [--w 2.5] [--seed 1234] [--every 1] [--graph]
  *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS] [--widom K]
- *         [--sk HMAX] [--gcmc Z [--gc-moves K] [--gc-every M]]
+ *         [--sk HMAX] [--profile AXIS[:NBINS]] [--gcmc Z [--gc-moves K] [--gc-every M]]
  *
  * --dump writes create_dump frames (kernel.cu:510-536; the reference's VISUALISATION path) of the
  * initial state and after every --every sweeps; --save writes a PMCSNAP1 snapshot at the end;
@@ -20,6 +20,11 @@
  * --sk HMAX (<= 1024) evaluates the density modes of the final state (pmc_density_modes) at (h,0,0),
  * (0,h,0), (0,0,h) for h = 1..HMAX and prints one `sk` line per h with |k| = 2 pi h / L and the mean
  * of the three S(k) = |rho(k)|^2 / N, then a closing `structure` line with N.
+ * --profile AXIS[:NBINS] (AXIS 0, 1 or 2; NBINS defaults to 4 per cell along the axis) samples the axis
+ * profiles of the final state (pmc_profiles): one `profile` line per bin with the bin centre, the
+ * density, P_N and P_T (ideal part rho / beta plus 12 vir / 2^32 / bin volume; each pair half in each
+ * partner's bin), one `pressure_tensor` line with the box-averaged P_xx, P_yy, P_zz and one
+ * `surface_tension` line with L_axis / 2 (P_N - P_T) for two interfaces.
  *
  * --gcmc Z samples the grand-canonical ensemble at activity Z = exp(beta mu) / Lambda^3 (pmc_start_gc):
  * after every sweep s with (s + 1) % M == 0 (--gc-every, default 1) one exchange sweep of K insert /
@@ -49,6 +54,7 @@ int main(int argc, char** argv) {
     p.w = 2.5f; p.beta = 0.3f; p.sigma = 0.5f; p.seed = 1234;
     long long atoms = 64;
     int passes = 1000, every = 1, graph = 0, pairobs = 0, widom = 0, sk = 0, gc_moves = 1, gc_every = 1;
+    int prof_axis = -1, prof_bins = 0;
     float gcmc = 0.0f;
     const char *dump = NULL, *save = NULL, *restart = NULL;
     for (int i = 1; i < argc; ++i) {
@@ -71,6 +77,16 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--pairobs")) { pairobs = atoi(v); ++i; }
         else if (!strcmp(a, "--widom")) { widom = atoi(v); ++i; }
         else if (!strcmp(a, "--sk")) { sk = atoi(v); ++i; }
+        else if (!strcmp(a, "--profile")) {
+            const char* colon = strchr(v, ':');
+            prof_axis = atoi(v);
+            prof_bins = colon ? atoi(colon + 1) : 0;
+            if (prof_axis < 0 || prof_axis > 2 || (colon && prof_bins < 1)) {
+                fprintf(stderr, "--profile AXIS[:NBINS]: AXIS 0..2, NBINS >= 1\n");
+                return 2;
+            }
+            ++i;
+        }
         else if (!strcmp(a, "--gcmc")) { gcmc = (float)atof(v); ++i; }
         else if (!strcmp(a, "--gc-moves")) { gc_moves = atoi(v); ++i; }
         else if (!strcmp(a, "--gc-every")) { gc_every = atoi(v); ++i; }
@@ -226,6 +242,40 @@ int main(int argc, char** argv) {
         free(hkl);
         free(re);
         free(im);
+    }
+    if (prof_axis >= 0) {
+        pmc_params q;
+        pmc_profile_obs fo;
+        if ((rc = pmc_get_params(ctx, &q))) die("pmc_get_params", rc);
+        const int cps[3] = {q.cps_x, q.cps_y, q.cps_z};
+        const int nb = prof_bins ? prof_bins : 4 * cps[prof_axis];
+        uint64_t* cnt = calloc((size_t)nb, sizeof(uint64_t));
+        int64_t* vir = calloc(3 * (size_t)nb, sizeof(int64_t));
+        if (!cnt || !vir) die("calloc", 0);
+        if ((rc = pmc_profiles(ctx, prof_axis, nb, cnt, vir, &fo))) die("pmc_profiles", rc);
+        const double len[3] = {(double)((float)q.cps_x * q.w), (double)((float)q.cps_y * q.w),
+                               (double)((float)q.cps_z * q.w)};
+        const double vol = len[0] * len[1] * len[2], width = len[prof_axis] / nb, vbin = vol / nb;
+        const int t0 = (prof_axis + 1) % 3, t1 = (prof_axis + 2) % 3;
+        double tot[3] = {0.0, 0.0, 0.0};
+        printf("# profile along axis %d: bin centre, rho, P_N, P_T\n", prof_axis);
+        for (int b = 0; b < nb; ++b) {
+            double conf[3];
+            for (int d = 0; d < 3; ++d) {
+                conf[d] = 12.0 * (double)vir[(size_t)d * (size_t)nb + (size_t)b] / 4294967296.0;
+                tot[d] += conf[d];
+            }
+            const double rho = (double)cnt[b] / vbin, ideal = rho / (double)q.beta;
+            printf("profile %.9g %.9g %.9g %.9g\n", -0.5 * len[prof_axis] + (b + 0.5) * width, rho,
+                   ideal + conf[prof_axis] / vbin, ideal + 0.5 * (conf[t0] + conf[t1]) / vbin);
+        }
+        const double ideal = (double)fo.particles / (vol * (double)q.beta);
+        printf("pressure_tensor %.9g %.9g %.9g (N %lld, ordered pairs %lld)\n", ideal + tot[0] / vol, ideal + tot[1] / vol,
+               ideal + tot[2] / vol, (long long)fo.particles, (long long)fo.pairs);
+        printf("surface_tension %.9g (axis %d, two interfaces)\n",
+               0.5 * len[prof_axis] * (tot[prof_axis] - 0.5 * (tot[t0] + tot[t1])) / vol, prof_axis);
+        free(cnt);
+        free(vir);
     }
     pmc_destroy(ctx);
     return 0;

@@ -57,6 +57,12 @@ class SkObs(C.Structure):
     _fields_ = [("particles", C.c_int64)]
 
 
+class ProfileObs(C.Structure):
+    """``pmc_profile_obs``."""
+
+    _fields_ = [("virial_fixed", C.c_int64), ("pairs", C.c_int64), ("particles", C.c_int64)]
+
+
 class GcStats(C.Structure):
     """``pmc_gc_stats``."""
 
@@ -81,6 +87,7 @@ PMC_IPC_HANDLE_BYTES = 1024     # include/pmc.h
 PMC_LAYOUT_REFERENCE, PMC_LAYOUT_PACKED = 0, 1
 PMC_PROBE_INSERT, PMC_PROBE_REAL = 0, 1     # include/pmc_probe.h
 PMC_SK_MAX_K, PMC_SK_MAX_H = 4096, 1024     # include/pmc_sk.h
+PMC_PROFILE_MAX_BINS, PMC_PROFILE_BINS_PER_CELL = 4096, 64     # include/pmc_profile.h
 
 
 class PmcError(RuntimeError):
@@ -180,6 +187,7 @@ def lib():
         _sig(L, "pmc_probe_energies", i32, _vp, i32, i32, u32, C.c_float, C.c_float, i32, _vp, _vp,
              C.POINTER(ProbeObs))
         _sig(L, "pmc_density_modes", i32, _vp, _vp, i32, _vp, _vp, C.POINTER(SkObs))
+        _sig(L, "pmc_profiles", i32, _vp, i32, i32, _vp, _vp, C.POINTER(ProfileObs))
         _sig(L, "pmc_exchange_phase", i32, _vp, i32, u32, C.c_float, i32)
         _sig(L, "pmc_exchange_sweep", i32, _vp, u32, C.c_float, i32)
         _sig(L, "pmc_gc_stats_read", i32, _vp, C.POINTER(GcStats), i32)

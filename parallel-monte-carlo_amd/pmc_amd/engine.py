@@ -21,8 +21,8 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT, PMC_PROBE_REAL, GcStats, PairObs, Params, ProbeObs, Result,
-                   SkObs, Stats, check, lib)
+from ._lib import (PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT, PMC_PROBE_REAL, GcStats, PairObs, Params, ProbeObs,
+                   ProfileObs, Result, SkObs, Stats, check, lib)
 
 FIX_SCALE = 2.0 ** 32
 
@@ -382,6 +382,35 @@ class PmcContext:
         w = np.float32(self.w)
         L = np.array([np.float32(self.cps_x) * w, np.float32(self.cps_y) * w, np.float32(self.cps_z) * w], np.float32)
         return {"hkl": h, "re": re, "im": im, "particles": int(out.particles), "L": L}
+
+    def profiles(self, axis: int = 2, nbins: Optional[int] = None) -> dict:
+        """Profiles along box axis ``axis`` (0 x, 1 y, 2 z) of the owned cells' particles
+        (pmc_profiles, include/pmc_profile.h) over nbins equal bins from -L/2 (default 4 per cell
+        along the axis; at most min(4096, 64 per cell)).  Returns count (uint64, particles per bin),
+        vir (3 x nbins int64: the ordered-pair sums of the diagonal virial components v d_d^2 / r^2 in
+        2^-32 units, each pair in its own particle's bin), virial_fixed and pairs (pair_observables'
+        integers), particles, axis, and the box lengths L as float32.  Integer sums over global
+        coordinates: slab ranks and samples add key by key (observables.add_profiles);
+        observables.density_profile, pressure_profile, pressure_tensor and surface_tension convert.
+
+        Averaging over sweeps: shiftCells translates EVERY coordinate by the sweep plan's d along its
+        axis f each sweep, so the whole configuration drifts rigidly through the periodic box and a
+        feature (a slab, a film) moves between samples.  Profiles of different sweeps must be
+        aligned first: roll each by observables.profile_translation(seed, first, count, w, flags,
+        axis) -- or by observables.centre_profile(count) -- before they are added.  The box averages
+        (pressure_tensor, surface_tension) do not depend on the alignment."""
+        cps_a = (self.cps_x, self.cps_y, self.cps_z)[axis] if axis in (0, 1, 2) else 0
+        nb = 4 * cps_a if nbins is None else int(nbins)
+        count = np.zeros(max(nb, 0), np.uint64)
+        vir = np.zeros((3, max(nb, 0)), np.int64)
+        out = ProfileObs()
+        check("pmc_profiles",
+              lib().pmc_profiles(self._h, int(axis), nb, count.ctypes.data if count.size else None,
+                                 vir.ctypes.data if vir.size else None, C.byref(out)))
+        w = np.float32(self.w)
+        L = np.array([np.float32(self.cps_x) * w, np.float32(self.cps_y) * w, np.float32(self.cps_z) * w], np.float32)
+        return {"count": count, "vir": vir, "virial_fixed": int(out.virial_fixed), "pairs": int(out.pairs),
+                "particles": int(out.particles), "axis": int(axis), "L": L}
 
     def stats(self, reset: bool = False) -> dict:
         s = Stats()

@@ -2,7 +2,9 @@
 ``PmcContext.pair_observables`` (pmc_pair_observables, include/pmc_pairobs.h), and the excess
 chemical potential and energy distributions from those of ``PmcContext.probe_energies``
 (pmc_probe_energies, include/pmc_probe.h), and the static structure factor S(k) from the density
-modes of ``PmcContext.density_modes`` (pmc_density_modes, include/pmc_sk.h).
+modes of ``PmcContext.density_modes`` (pmc_density_modes, include/pmc_sk.h), and the density and
+pressure-tensor profiles and the surface tension from the axis profiles of ``PmcContext.profiles``
+(pmc_profiles, include/pmc_profile.h).
 
 Pure numpy, no GPU: the sums of several slab contexts are added first (they are exact integers),
 then converted here.  Units are the library's reduced Lennard-Jones units (epsilon = sigma_LJ = 1).
@@ -174,6 +176,105 @@ def structure_factor(res: dict) -> tuple:
     re = np.asarray(res["re"], np.int64).astype(np.float64) / FIX_SCALE
     im = np.asarray(res["im"], np.int64).astype(np.float64) / FIX_SCALE
     return k, (re * re + im * im) / float(res["particles"])
+
+
+# ---- axis profiles (PmcContext.profiles, include/pmc_profile.h) ----------------------------------
+
+_PROFILE_SUMS = ("virial_fixed", "pairs", "particles")
+
+
+def add_profiles(a: dict, b: dict) -> dict:
+    """Key-wise sum of two profile results over the same axis, bins and box: the slab ranks of one
+    sample, or several samples (every entry is an exact integer sum; align samples of different
+    sweeps first, see PmcContext.profiles).  Refuses results whose axis, number of bins or box
+    differ."""
+    if (int(a["axis"]) != int(b["axis"]) or len(a["count"]) != len(b["count"])
+            or not np.array_equal(a["L"], b["L"])):
+        raise ValueError("add_profiles: results over different axes, bins or box lengths")
+    out = dict(a)
+    out["count"] = np.asarray(a["count"], np.uint64) + np.asarray(b["count"], np.uint64)
+    out["vir"] = np.asarray(a["vir"], np.int64) + np.asarray(b["vir"], np.int64)
+    for k in _PROFILE_SUMS:
+        out[k] = int(a[k]) + int(b[k])
+    return out
+
+
+def _profile_geometry(res: dict) -> tuple:
+    """(axis, nbins, L_a, bin width, cross-section area) of a profile result, in float64."""
+    L = np.asarray(res["L"], np.float64)
+    a = int(res["axis"])
+    nb = len(res["count"])
+    return a, nb, float(L[a]), float(L[a]) / nb, float(np.prod(L) / L[a])
+
+
+def density_profile(res: dict, samples: int = 1) -> tuple:
+    """(bin centres, rho): rho_b = count_b / (A * width) with A the box cross-section normal to the
+    axis; bin 0 starts at -L_a / 2.  samples: the number of added samples the sums hold."""
+    _, nb, La, width, area = _profile_geometry(res)
+    centres = -0.5 * La + (np.arange(nb) + 0.5) * width
+    return centres, np.asarray(res["count"], np.float64) / (area * width * samples)
+
+
+def pressure_profile(res: dict, beta: float, samples: int = 1) -> tuple:
+    """(bin centres, P_N, P_T): the ideal part rho_b / beta plus the configurational part
+    12 * vir[d][b] / 2^32 / (bin volume); P_N takes d = the axis, P_T the mean of the other two.
+    Each pair is assigned half to each partner's bin (a Harasima-type tangential profile; the normal
+    profile under this assignment is NOT flat through an interface: only its box average and
+    P_N - P_T integrated over the box are contour-independent)."""
+    a, _, _, width, area = _profile_geometry(res)
+    centres, rho = density_profile(res, samples)
+    conf = 12.0 * np.asarray(res["vir"], np.int64).astype(np.float64) / FIX_SCALE / (area * width * samples)
+    others = [d for d in range(3) if d != a]
+    ideal = rho / float(beta)
+    return centres, ideal + conf[a], ideal + 0.5 * (conf[others[0]] + conf[others[1]])
+
+
+def pressure_tensor(res: dict, beta: float, samples: int = 1) -> tuple:
+    """Box-averaged (P_xx, P_yy, P_zz): particles / (V beta) + 12 * sum_b vir[d][b] / 2^32 / V.  Their
+    mean is the scalar virial pressure of observables.pressure up to the roundings of
+    pmc_profile.h's error budget."""
+    vol = float(np.prod(np.asarray(res["L"], np.float64)))
+    ideal = float(res["particles"]) / (vol * float(beta) * samples)
+    tot = [int(np.asarray(res["vir"], np.int64)[d].astype(object).sum()) for d in range(3)]
+    return tuple(ideal + 12.0 * t / FIX_SCALE / (vol * samples) for t in tot)
+
+
+def surface_tension(res: dict, beta: float = 1.0, interfaces: int = 2, samples: int = 1) -> float:
+    """gamma = L_a / interfaces * (P_N - P_T) from the box averages (P_T the mean of the two
+    tangential components); the ideal parts cancel, so beta does not enter the value."""
+    p = pressure_tensor(res, beta, samples)
+    a = int(res["axis"])
+    others = [d for d in range(3) if d != a]
+    La = float(np.asarray(res["L"], np.float64)[a])
+    return La / interfaces * (p[a] - 0.5 * (p[others[0]] + p[others[1]]))
+
+
+def centre_profile(count) -> int:
+    """The roll (np.roll(profile, roll)) that puts the circular centre of mass of the count profile
+    at the box centre (between bins nbins/2 - 1 and nbins/2): the angle of sum_b count_b
+    exp(2 pi i (b + 1/2) / nbins).  0 for an empty or perfectly uniform profile."""
+    c = np.asarray(count, np.float64)
+    nb = c.size
+    z = np.sum(c * np.exp(2j * np.pi * (np.arange(nb) + 0.5) / nb))
+    if nb == 0 or abs(z) <= 1e-12 * max(float(c.sum()), 1.0):
+        return 0
+    com = (np.angle(z) % (2.0 * np.pi)) / (2.0 * np.pi) * nb      # in bins, [0, nb)
+    return int(np.round(0.5 * nb - com)) % nb
+
+
+def profile_translation(seed: int, first: int, count: int, w: float = 2.5, flags: int = 0, axis: int = 2) -> float:
+    """The rigid translation along ``axis`` that sweeps first .. first + count - 1 apply to every
+    coordinate: shiftCells moves x_f to x_f - d with (f, d) of the sweep plan (pmc_sweep_plan_ex), so
+    the result is minus the sum of d over the sweeps whose f is the axis (float64; modulo L_a the
+    configuration is that of no shifts moved by this much).  A profile sampled after those sweeps is
+    brought back to the frame of sweep ``first`` by np.roll(profile, -round(translation / width))."""
+    from .plan import sweep_plan
+    t = 0.0
+    for s in range(int(first), int(first) + int(count)):
+        _, f, d = sweep_plan(seed, s, w, flags)
+        if f == axis:
+            t -= float(d)
+    return t
 
 
 def shell_average(k, s, dk: float) -> tuple:
