@@ -1682,8 +1682,11 @@ __global__ __launch_bounds__(kShiftThreads) void k_shift_run(DevGeom g, const fl
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             const int nw = nnew > nm ? nm : nnew;
             // whole lines counted from the record's start, capped at the record's own 3*nm/4 units: a
-            // record that is not a whole number of lines (nm = 4, 8, 12, 20, ...) never spills into
-            // the next cell's record or past the buffer
+            // record of whole 16-B units that is not a whole number of 64-B lines (nm a multiple of 4
+            // but not of 16: 4, 8, 12, 20, 24, ...) never spills into the next cell's record or past
+            // the buffer.  Every other length (nm no multiple of 4: 1, 2, 3, 5, ..., 63) has records
+            // that do not start on 16-B boundaries and never comes here: it takes the per-slot stores
+            // of the else branch below (tests/test_gpu_row_lengths.py)
             int units = (12 * nw + 63) / 64 * 4;
             if (units > 3 * nm / 4) units = 3 * nm / 4;
             if (j < L && p < units) {
