@@ -402,7 +402,7 @@ int pmc_density_modes(pmc_ctx* ctx, const int32_t* h_hkl, int nk, int64_t* h_re,
  * pairs (i in bin b, j in i's 27-cell stencil, inside the cutoff) of fixed(v d_d^2 / r^2): the
  * diagonal pair-virial components in the quarter units of the virial sum, each unordered pair half in
  * each partner's bin.  From them: the density profile, the pressure-tensor profiles P_N and P_T
- * (Harasima-type assignment; the local NORMAL profile is not flat through an interface under it), the
+ * (Harasima-type assignment; for the local NORMAL pressure call pmc_profiles_ik below), the
  * box-averaged tensor and the surface tension, which are exact with respect to the contour
  * (pmc_amd.observables).  The reference has no such observable (its only one is calc_energy,
  * kernel.cu:452-470).  h_count (nbins counters) and h_vir (3 * nbins sums, 2^-32 units) are HOST
@@ -418,6 +418,15 @@ typedef struct pmc_profile_obs {
     int64_t particles;     /* particles in owned cells */
 } pmc_profile_obs;
 int pmc_profiles(pmc_ctx* ctx, int axis, int nbins, uint64_t* h_count, int64_t* h_vir, pmc_profile_obs* out);
+/* The same profiles on the Irving-Kirkwood contour, defined bit for bit in pmc_profile_ik.h: h_count and
+ * *out are pmc_profiles', and h_ik[d * nbins + b] takes, of every ordered pair's fixed(v d_d^2 / r^2),
+ * the part of the straight segment between the two partners that lies in bin b along the axis
+ * (integer position words, exact integer shares that add up to the pair's value).  P_N from h_ik is
+ * the local normal pressure, flat through an equilibrated planar interface, and P_N - P_T locates the
+ * tension; sum_b h_ik[d][b] == sum_b h_vir[d][b] of pmc_profiles bit for bit, so the box tensor and the
+ * surface tension are the same.  Arguments, PMC_ERR_ARG cases, stream, synchronisation and what is
+ * left unchanged: as for pmc_profiles.  Additive over slab ranks without a reduction. */
+int pmc_profiles_ik(pmc_ctx* ctx, int axis, int nbins, uint64_t* h_count, int64_t* h_ik, pmc_profile_obs* out);
 /* ---- grand-canonical exchange moves (mu V T) ------------------------------------------------
  * Insertions and deletions as a further kind of colour phase, defined bit for bit in pmc_gc.h: every
  * owned cell of the colour runs k_per_cell (1..64) attempts in order on its own particle list, each

@@ -787,15 +787,20 @@ int pmc_density_modes(pmc_ctx* c, const int32_t* h_hkl, int nk, int64_t* h_re, i
     return PMC_OK;
 }
 
-int pmc_profiles(pmc_ctx* c, int axis, int nbins, uint64_t* h_count, int64_t* h_vir, pmc_profile_obs* out) {
+namespace {
+
+// pmc_profiles and pmc_profiles_ik: the same checks, accumulator and host sum around their launchers
+int profiles_call(pmc_ctx* c, const char* fn, decltype(&launch_profile) launch, int axis, int nbins, uint64_t* h_count,
+                  int64_t* h_vir, pmc_profile_obs* out) {
+    const std::string f(fn);
     if (!c || !h_count || !h_vir || !out) return fail(PMC_ERR_ARG, "bad argument");
-    if (axis < 0 || axis > 2) return fail(PMC_ERR_ARG, "pmc_profiles: axis must be 0, 1 or 2");
+    if (axis < 0 || axis > 2) return fail(PMC_ERR_ARG, f + ": axis must be 0, 1 or 2");
     const int cps_a = axis == 0 ? c->G.cps_x : (axis == 1 ? c->G.cps_y : c->G.cps_z);
     if (nbins < 1 || nbins > pmc_profile_max_bins(cps_a))
-        return fail(PMC_ERR_ARG, "pmc_profiles: nbins must be in 1..min(4096, 64 * cells along the axis)");
+        return fail(PMC_ERR_ARG, f + ": nbins must be in 1..min(4096, 64 * cells along the axis)");
     // the kernel reads both halos, as the energy does (energy_fixed)
     if (slab_pending_zdir(c))
-        return fail(PMC_ERR_ARG, "pmc_profiles: a slab halo exchange is pending (call pmc_slab_finish first)");
+        return fail(PMC_ERR_ARG, f + ": a slab halo exchange is pending (call pmc_slab_finish first)");
     if (int rj = slab_join(c)) return rj;
     const size_t per = (size_t)kProfHead + 4 * (size_t)nbins;
     if (nbins > c->prof_cap) {   // allocated on first use, grown with nbins
@@ -809,7 +814,7 @@ int pmc_profiles(pmc_ctx* c, int axis, int nbins, uint64_t* h_count, int64_t* h_
         c->prof_cap = nbins;
     }
     PMC_HIP(hipMemsetAsync(c->prof_acc, 0, sizeof(unsigned long long) * kProfCopies * per, c->stream));
-    hipError_t e = launch_profile(c->G, c->disk[c->cur], c->n[c->cur], c->prof_acc, axis, nbins, c->stream);
+    hipError_t e = launch(c->G, c->disk[c->cur], c->n[c->cur], c->prof_acc, axis, nbins, c->stream);
     if (e != hipSuccess) return hip_fail(e, "axis profiles launch");
     std::vector<unsigned long long> h((size_t)kProfCopies * per);
     PMC_HIP(hipMemcpyAsync(h.data(), c->prof_acc, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost,
@@ -824,6 +829,16 @@ int pmc_profiles(pmc_ctx* c, int axis, int nbins, uint64_t* h_count, int64_t* h_
     for (int b = 0; b < nbins; ++b) h_count[b] = (uint64_t)s[(size_t)kProfHead + (size_t)b];
     for (size_t b = 0; b < 3 * (size_t)nbins; ++b) h_vir[b] = (int64_t)s[(size_t)kProfHead + (size_t)nbins + b];
     return PMC_OK;
+}
+
+}  // namespace
+
+int pmc_profiles(pmc_ctx* c, int axis, int nbins, uint64_t* h_count, int64_t* h_vir, pmc_profile_obs* out) {
+    return profiles_call(c, "pmc_profiles", launch_profile, axis, nbins, h_count, h_vir, out);
+}
+
+int pmc_profiles_ik(pmc_ctx* c, int axis, int nbins, uint64_t* h_count, int64_t* h_ik, pmc_profile_obs* out) {
+    return profiles_call(c, "pmc_profiles_ik", launch_profile_ik, axis, nbins, h_count, h_ik, out);
 }
 
 // ---- grand-canonical exchange moves (pmc_gc.h) --------------------------------------------------

@@ -204,6 +204,11 @@ constexpr int kProfWin = 96;         // bins of a wave's LDS window (a cell touc
 static_assert((kProfCopies & (kProfCopies - 1)) == 0, "accumulator copies: a power of two");
 hipError_t launch_profile(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int axis,
                           int nbins, hipStream_t st);
+// the same on the Irving-Kirkwood contour (k_profile_ik, pmc_profile_ik.h): launch_profile's accumulator
+// layout with the spread sums in place of vir
+constexpr int kProfIkWin = 200;      // bins of a wave's LDS window (a cell's three-cell span: at most 3 * 64 + 4)
+hipError_t launch_profile_ik(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int axis,
+                             int nbins, hipStream_t st);
 // the cells of one colour of one plane: mode 0 plane -> packed buffer, 1 packed -> plane,
 // 2 plane -> plane; (cps_x/2)*(cps_y/2)*3*nmax floats
 hipError_t launch_colour_rows(const DevGeom& g, const float* src, float* dst, int colour, int mode, hipStream_t st);

@@ -30,6 +30,7 @@
 #include "../../include/pmc_gc.h"
 #include "../../include/pmc_sk.h"
 #include "../../include/pmc_profile.h"
+#include "../../include/pmc_profile_ik.h"
 
 namespace pmc {
 
@@ -3493,6 +3494,325 @@ __global__ __launch_bounds__(kWave) void k_profile(DevGeom g, const float* __res
 }
 
 // ------------------------------------------------------------------------------------------
+// axis profiles on the Irving-Kirkwood contour (include/pmc_profile_ik.h): k_profile's counts and
+// totals, but every ordered pair's three fixed-point terms are SPREAD over the bins its segment
+// crosses along the axis.  k_profile's stencil, staging (with a fourth staged value: the t word of
+// the partner's STORED axis coordinate, taken before the image shift is added), filter, grid and
+// pair loop (own particle i by readlane, lanes = staged partners).  Per in-cutoff lane:
+//   - the whole pair in i's own bin (S = 0, or a segment inside that bin): three per-lane int64
+//     sums, one wave reduction per particle, no atomics -- k_profile's path;
+//   - the whole pair in one other bin: one deposit of T;
+//   - otherwise the lane walks bins k0..k1 (at most 66 trips, divergent): one boundary per trip
+//     (pmc_ik_boundary), m = clamp(B_{k+1} - lo), C_d(m) for the three components (pmc_ik_cum) and the
+//     deposit of C_d(m) - C_d(previous m).  The previous bin's upper value IS this bin's lower one
+//     (the same function of the same arguments), and C_d(0) = 0 at the first bin because
+//     B_{k0} <= lo: the same integers as evaluating both ends per bin.  The divisions are
+//     pmc_ik_floordiv's (a float64 estimate, the exact int64 remainder decides).
+// A deposit adds to the wave's WINDOW in LDS with returnless 64-bit LDS atomics: kProfIkWin
+// consecutive bins, int64 sums and u32 counts, indexed by (bin - anchor) modulo nbins, so a box of
+// at most kProfIkWin bins lives in the window whole and the wrapped edge needs nothing special
+// there.  The anchor is the first bin of the three-cell span of the cell along the axis,
+// [floor((c - 1) nbins / cps) - 1, floor((c + 2) nbins / cps) + 1] (<= 3 * 64 + 4 bins); when a cell's
+// span does not fit the current window it is flushed (64-bit global atomics, nonzero entries only)
+// and re-anchored.  A deposit whose bin is outside the window (the wrapped edge of a finer
+// profile, a coordinate a few ulp outside its cell) adds straight to the global accumulator.
+// Integer sums only: exact in any order, equal to tests/profile_ik_ref.c bit for bit.
+// ------------------------------------------------------------------------------------------
+template <int NSLOT, bool OFF32>
+__global__ __launch_bounds__(kWave) void k_profile_ik(DevGeom g, const float* __restrict__ disk,
+                                                      const int16_t* __restrict__ ncnt,
+                                                      unsigned long long* __restrict__ acc, uint32_t total_cells,
+                                                      int axis, int nbins, int cps_a, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float psm[];
+    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
+    constexpr int CPP = kWave / HS;    // cells per staging pass
+    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
+    constexpr int W = kProfIkWin;
+    using DA = DiskAddr<OFF32>;
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int cap = 27 * nm;
+    unsigned long long* wvir = (unsigned long long*)psm;        // [3][W] int64 sums of the window
+    unsigned* wcnt = (unsigned*)(wvir + 3 * W);                 // [W] counts of the window
+    int* inv_l = (int*)(wcnt + W);                              // list entry -> stencil lane (32 ints)
+    float* ex_ = (float*)(inv_l + 32);
+    float* ey_ = ex_ + cap;
+    float* ez_ = ex_ + 2 * cap;
+    uint32_t* ew_ = (uint32_t*)(ex_ + 3 * cap);                 // t word of the stored axis coordinate
+    const int p = lane % HS;
+    const int ee = lane / HS;
+    const float rc2 = g.rc2;
+    const double inv_nb = 1.0 / (double)nbins;
+    const int wn = nbins < W ? nbins : W;          // window entries in use
+    long long sum = 0;                             // per lane: the virial total
+    unsigned long long n_pairs = 0, n_part = 0;    // wave-uniform
+    for (int b = lane; b < W; b += kWave) {
+        wcnt[b] = 0u;
+        wvir[b] = wvir[W + b] = wvir[2 * W + b] = 0ull;
+    }
+    if (lane < 32) inv_l[lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kProfCopies - 1)) * ((size_t)kProfHead + 4 * (size_t)nbins);
+    unsigned long long* gcnt = mine + kProfHead;
+    unsigned long long* gvir = gcnt + nbins;       // [3][nbins]
+    int wraw = 0;                                  // the window's first bin as the span counts it (may be < 0)
+    int wmod = 0;                                  // ... modulo nbins: entry e holds bin (wmod + e) mod nbins
+    // the window's nonzero entries to the global accumulator, the window zeroed
+    auto flush_window = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        for (int e = lane; e < wn; e += kWave) {
+            int b = wmod + e;
+            b = b >= nbins ? b - nbins : b;        // wmod < nbins, e < nbins
+            const unsigned cn = wcnt[e];
+            const unsigned long long a0 = wvir[e], a1 = wvir[W + e], a2 = wvir[2 * W + e];
+            if (cn) atomicAdd(&gcnt[b], (unsigned long long)cn);
+            if (a0) atomicAdd(&gvir[b], a0);
+            if (a1) atomicAdd(&gvir[(size_t)nbins + b], a1);
+            if (a2) atomicAdd(&gvir[2 * (size_t)nbins + b], a2);
+            wcnt[e] = 0u;
+            wvir[e] = wvir[W + e] = wvir[2 * W + e] = 0ull;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    };
+    // three sums into bin b (0 <= b < nbins): the window, or the global accumulator outside it
+    auto deposit = [&](int b, long long sx, long long sy, long long sz) {
+        int e = b - wmod;
+        e = e < 0 ? e + nbins : e;
+        if (e < wn) {
+            if (sx) (void)__hip_atomic_fetch_add(&wvir[e], (unsigned long long)sx, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (sy) (void)__hip_atomic_fetch_add(&wvir[W + e], (unsigned long long)sy, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (sz) (void)__hip_atomic_fetch_add(&wvir[2 * W + e], (unsigned long long)sz, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else {
+            if (sx) atomicAdd(&gvir[b], (unsigned long long)sx);
+            if (sy) atomicAdd(&gvir[(size_t)nbins + b], (unsigned long long)sy);
+            if (sz) atomicAdd(&gvir[2 * (size_t)nbins + b], (unsigned long long)sz);
+        }
+    };
+
+    // rows of the cell in flight (k_pairobs' issue_rows): slots [0, HS) of its occupied stencil cells
+    // (own cell: entry 0 when occupied), in registers; vw: the t word of the stored axis coordinate
+    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
+    uint32_t vw[NPMAX];
+    bool vact[NPMAX];
+    int ncells = 0;
+    auto issue_rows = [&](const PairObsStencil& st) {
+        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
+        ncells = __popcll(mo);
+        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int q = 0; q < NPMAX; ++q) {
+            const int e = q * CPP + ee;
+            const int src = inv_l[e < ncells ? e : 0];
+            const int c_cnt = __shfl(st.cnt, src);
+            const int c_idx = __shfl(st.kc, src);
+            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
+            vact[q] = e < ncells && p < c_cnt;
+            vx[q] = vy[q] = vz[q] = 0.0f;
+            vw[q] = 0u;
+            if (vact[q]) {
+                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
+                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
+                vw[q] = pmc_ik_word(pmc_sk_word(axis == 0 ? vx[q] : (axis == 1 ? vy[q] : vz[q]), scale));
+                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
+                vy[q] = vy[q] + isy;
+                vz[q] = vz[q] + isz;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
+    };
+
+    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
+    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
+        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
+        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
+        issue_rows(cur);
+        PairObsStencil nxt = cur;
+        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
+        for (int c = 0; c < ncl; ++c) {
+            // ---- stage cell c (k_pairobs' staging): own particles first, then the filtered partners
+            float blo[3], bhi[3];
+            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
+            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
+            const int ca = axis == 0 ? cur.x : (axis == 1 ? cur.y : cur.zg);   // the cell along the axis
+            int S = 0;
+            auto put = [&](bool act, float ux, float uy, float uz, uint32_t uw) {
+                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+                if (act) {
+                    const int dst = S + mbcnt64(am);
+                    ex_[dst] = ux;
+                    ey_[dst] = uy;
+                    ez_[dst] = uz;
+                    ew_[dst] = uw;
+                }
+                S += __popcll(am);
+            };
+            // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles
+            auto chunks = [&](unsigned long long mg, bool filter) {
+                if constexpr (NSLOT > HS) {
+                    for (int s0 = HS; s0 < nm; s0 += HS) {
+                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
+                        while (ov) {
+                            int ks = 0, nc = 0;
+                            for (; nc < CPP && ov; ++nc) {
+                                const int kb = (int)__builtin_ctzll(ov);
+                                ov &= ov - 1ull;
+                                ks = ee == nc ? kb : ks;
+                            }
+                            const int c_cnt = __shfl(cur.cnt, ks);
+                            const int c_idx = __shfl(cur.kc, ks);
+                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
+                            const int ps = s0 + p;
+                            const bool act = ee < nc && ps < c_cnt;
+                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+                            uint32_t uw = 0u;
+                            if (act) {
+                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
+                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+                                uw = pmc_ik_word(pmc_sk_word(axis == 0 ? ux : (axis == 1 ? uy : uz), scale));
+                                ux = ux + isx;
+                                uy = uy + isy;
+                                uz = uz + isz;
+                            }
+                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz, uw);
+                        }
+                    }
+                }
+            };
+            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
+            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
+            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0], vw[0]);      // own slots [0, HS)
+            chunks(1ull, false);                                          // own slots [HS, n)
+#pragma unroll
+            for (int q = 0; q < NPMAX; ++q) {
+                const int e = q * CPP + ee;
+                if (q * CPP < ncells)
+                    put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q], vw[q]);
+            }
+            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            // ---- the next cell's rows go out now and arrive while this cell's pairs run
+            if (c + 1 < ncl) {
+                cur = nxt;
+                issue_rows(cur);
+                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
+            }
+            n_part += (unsigned long long)n_own;
+            if (n_own == 0) continue;
+            // ---- the window holds this cell's three-cell span, or is flushed and re-anchored at it
+            //      (a box of at most W bins is in the window whole: never re-anchored)
+            if (nbins > W) {
+                const int lo_c = (int)(((uint32_t)(ca - 1 + cps_a) * (uint32_t)nbins) / (uint32_t)cps_a) - nbins - 1;
+                const int hi_c = (int)(((uint32_t)(ca + 2) * (uint32_t)nbins) / (uint32_t)cps_a) + 1;
+                if (lo_c < wraw || hi_c >= wraw + W) {
+                    flush_window();
+                    wraw = lo_c;
+                    wmod = lo_c < 0 ? lo_c + nbins : lo_c;   // lo_c >= -(nbins / cps_a + 2) > -nbins here
+                }
+            }
+            // ---- ordered pairs (i, j): own particle i (staged first: lane i of block 0) by readlane,
+            //      lane j holds staged partner j of the block; j == i skipped
+            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+            const uint32_t ow = ew_[lane];
+            const int j1 = kWave + lane < S ? kWave + lane : 0;
+            const float px = ex_[j1], py = ey_[j1], pz = ez_[j1];         // block 1
+            const uint32_t pw = ew_[j1];
+            long long mx = 0, my = 0, mz = 0;                             // lane i: particle i's own-bin sums
+            for (int i = 0; i < n_own; ++i) {
+                const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+                const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+                const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+                const uint32_t ti = (uint32_t)__builtin_amdgcn_readlane((int)ow, i);
+                const int bi = (int)pmc_profile_bin(ti - 0x80000000u, nbins);   // i's bin (wave-uniform)
+                long long ax = 0, ay = 0, az = 0;
+                auto block = [&](int jb, float xj, float yj, float zj, uint32_t tj, bool self) {
+                    const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
+                    const float r2 = pmc_r2(dx, dy, dz);
+                    const bool in = r2 <= rc2 && jb + lane < S && !self;
+                    const unsigned long long im = __builtin_amdgcn_ballot_w64(in);
+                    if (im == 0ull) return;
+                    n_pairs += (unsigned long long)__popcll(im);
+                    if (in) {
+                        const float v = pmc_virial_term(r2);
+                        const float inv = pmc_recip(__builtin_fmaxf(r2, PMC_R2_MIN));
+                        sum += pmc_to_fixed_f32(v);
+                        const long long Tx = pmc_to_fixed_f32(pmc_profile_term_inv(v, dx, inv));
+                        const long long Ty = pmc_to_fixed_f32(pmc_profile_term_inv(v, dy, inv));
+                        const long long Tz = pmc_to_fixed_f32(pmc_profile_term_inv(v, dz, inv));
+                        const int32_t s = pmc_ik_sep(ti, tj);
+                        const long long Sg = pmc_ik_len(s);
+                        const long long lo = pmc_ik_lo(ti, s);
+                        const long long k0 = pmc_ik_bin(lo, nbins);
+                        const long long k1 = Sg == 0 ? k0 : pmc_ik_bin(lo + Sg - 1, nbins);
+                        if (k0 == k1) {   // the whole pair in one bin (S = 0: lo = t_i + 2^32, i's bin)
+                            const int b = (int)pmc_ik_wrap(k0, nbins);
+                            if (b == bi) {
+                                ax += Tx;
+                                ay += Ty;
+                                az += Tz;
+                            } else {
+                                deposit(b, Tx, Ty, Tz);
+                            }
+                        } else {
+                            const double inv_s = 1.0 / (double)Sg;
+                            int64_t qx, rx, qy, ry, qz, rz;
+                            pmc_ik_split(Tx, Sg, inv_s, &qx, &rx);
+                            pmc_ik_split(Ty, Sg, inv_s, &qy, &ry);
+                            pmc_ik_split(Tz, Sg, inv_s, &qz, &rz);
+                            long long cx = 0, cy = 0, cz = 0;   // C_d(m_{k0}) = 0: B_{k0} <= lo
+                            int b = (int)pmc_ik_wrap(k0, nbins);
+                            for (long long k = k0; k <= k1; ++k) {
+                                const long long m = pmc_ik_clamp(pmc_ik_boundary(k + 1, nbins, inv_nb) - lo, Sg);
+                                const long long nx = pmc_ik_cum(Tx, qx, rx, m, Sg, inv_s);
+                                const long long ny = pmc_ik_cum(Ty, qy, ry, m, Sg, inv_s);
+                                const long long nz = pmc_ik_cum(Tz, qz, rz, m, Sg, inv_s);
+                                deposit(b, nx - cx, ny - cy, nz - cz);
+                                cx = nx;
+                                cy = ny;
+                                cz = nz;
+                                b = b + 1 == nbins ? 0 : b + 1;
+                            }
+                        }
+                    }
+                };
+                block(0, ox, oy, oz, ow, lane == i);
+                if (S > kWave) block(kWave, px, py, pz, pw, false);
+                for (int jb = 2 * kWave; jb < S; jb += kWave) {
+                    const int jj = jb + lane < S ? jb + lane : 0;
+                    block(jb, ex_[jj], ey_[jj], ez_[jj], ew_[jj], false);
+                }
+                const long long tx = wave_sum_i64(ax), ty = wave_sum_i64(ay), tz = wave_sum_i64(az);
+                if (lane == i) {
+                    mx = tx;
+                    my = ty;
+                    mz = tz;
+                }
+            }
+            // ---- lanes < n_own: the particle's count and own-bin sums into the window or, outside it,
+            //      the global accumulator
+            if (lane < n_own) {
+                const int b = (int)pmc_profile_bin(ow - 0x80000000u, nbins);
+                int e = b - wmod;
+                e = e < 0 ? e + nbins : e;
+                if (e < wn) (void)__hip_atomic_fetch_add(&wcnt[e], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                else atomicAdd(&gcnt[b], 1ull);
+                deposit(b, mx, my, mz);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+        }
+    }
+    // ---- flush: the window, then the wave sums (int64, exact in any order)
+    flush_window();
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    const unsigned long long head3 = lane == 0 ? (unsigned long long)sum : (lane == 1 ? n_pairs : n_part);
+    if (lane < kProfHead && head3 != 0) atomicAdd(&mine[lane], head3);
+}
+
+// ------------------------------------------------------------------------------------------
 // density modes (include/pmc_sk.h): rho(k) = sum_j exp(i k.r_j) over the owned cells' particles for
 // nk reciprocal-lattice vectors.  The other way round from every kernel above: the LANES are wave
 // vectors (blockIdx.y: blocks of 64), the particles are wave-uniform, and there is no stencil.  A
@@ -4527,6 +4847,29 @@ hipError_t launch_profile(const DevGeom& g, const float* disk, const int16_t* n,
         constexpr int NS = decltype(ns)::value;
         constexpr bool O = decltype(off)::value;
         hipLaunchKernelGGL((k_profile<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, axis, nbins,
+                           cps_a, scale);
+    });
+    return hipGetLastError();
+}
+
+// launch_profile's accumulator, grid and checks.  LDS per wave: the staged partners with their axis
+// words (16 B each, 27 * nmax of them), 32 list entries and the window of kProfIkWin bins (28 B
+// each): 12.5 KiB at nmax 16, whatever nbins.
+hipError_t launch_profile_ik(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int axis,
+                             int nbins, hipStream_t st) {
+    if (axis < 0 || axis > 2) return hipErrorInvalidValue;
+    const int cps_a = axis == 0 ? g.cps_x : (axis == 1 ? g.cps_y : g.cps_z);
+    if (nbins < 1 || nbins > pmc_profile_max_bins(cps_a) || nbins > kProfMaxBins) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
+    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
+    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
+    const size_t lds = sizeof(float) * (4 * 27 * (size_t)g.nmax + 32) + (size_t)kProfIkWin * (3 * 8 + 4);
+    const float scale = pmc_sk_scale(axis == 0 ? g.Lx : (axis == 1 ? g.Ly : g.Lz));
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
+    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
+        hipLaunchKernelGGL((k_profile_ik<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, axis, nbins,
                            cps_a, scale);
     });
     return hipGetLastError();

@@ -5,7 +5,8 @@
  *   start [--cps 4] [--atoms 64] [--passes 1000] [--nmax 16] [--moves 10] [--beta 0.3]
  *         [--sigma 0.5] [--w 2.5] [--seed 1234] [--every 1] [--graph]
  *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS] [--widom K]
- *         [--sk HMAX] [--profile AXIS[:NBINS]] [--gcmc Z [--gc-moves K] [--gc-every M]]
+ *         [--sk HMAX] [--profile AXIS[:NBINS]] [--profile-ik AXIS[:NBINS]]
+ *         [--gcmc Z [--gc-moves K] [--gc-every M]]
  *
  * --dump writes create_dump frames (kernel.cu:510-536; the reference's VISUALISATION path) of the
  * initial state and after every --every sweeps; --save writes a PMCSNAP1 snapshot at the end;
@@ -25,6 +26,10 @@
  * density, P_N and P_T (ideal part rho / beta plus 12 vir / 2^32 / bin volume; each pair half in each
  * partner's bin), one `pressure_tensor` line with the box-averaged P_xx, P_yy, P_zz and one
  * `surface_tension` line with L_axis / 2 (P_N - P_T) for two interfaces.
+ * --profile-ik AXIS[:NBINS] (the same defaults) does the same on the Irving-Kirkwood contour
+ * (pmc_profiles_ik: every pair spread over the bins between the partners, so P_N is the local normal
+ * pressure): `ik_profile` lines, then `ik_pressure_tensor` and `ik_surface_tension`, which equal the
+ * --profile ones (the bin sums' totals do not depend on the contour).
  *
  * --gcmc Z samples the grand-canonical ensemble at activity Z = exp(beta mu) / Lambda^3 (pmc_start_gc):
  * after every sweep s with (s + 1) % M == 0 (--gc-every, default 1) one exchange sweep of K insert /
@@ -47,6 +52,50 @@ static void die(const char* what, int rc) {
     exit(1);
 }
 
+/* --profile (ik 0, pmc_profiles) and --profile-ik (ik 1, pmc_profiles_ik): the table, the tensor and
+ * the surface tension; the IK lines carry the prefix ik_ */
+static void print_profiles(pmc_ctx* ctx, int prof_axis, int prof_bins, int ik) {
+    const char* pre = ik ? "ik_" : "";
+    int rc;
+    pmc_params q;
+    pmc_profile_obs fo;
+    if ((rc = pmc_get_params(ctx, &q))) die("pmc_get_params", rc);
+    const int cps[3] = {q.cps_x, q.cps_y, q.cps_z};
+    const int nb = prof_bins ? prof_bins : 4 * cps[prof_axis];
+    uint64_t* cnt = calloc((size_t)nb, sizeof(uint64_t));
+    int64_t* vir = calloc(3 * (size_t)nb, sizeof(int64_t));
+    if (!cnt || !vir) die("calloc", 0);
+    if (ik) {
+        if ((rc = pmc_profiles_ik(ctx, prof_axis, nb, cnt, vir, &fo))) die("pmc_profiles_ik", rc);
+    } else if ((rc = pmc_profiles(ctx, prof_axis, nb, cnt, vir, &fo))) {
+        die("pmc_profiles", rc);
+    }
+    const double len[3] = {(double)((float)q.cps_x * q.w), (double)((float)q.cps_y * q.w),
+                           (double)((float)q.cps_z * q.w)};
+    const double vol = len[0] * len[1] * len[2], width = len[prof_axis] / nb, vbin = vol / nb;
+    const int t0 = (prof_axis + 1) % 3, t1 = (prof_axis + 2) % 3;
+    double tot[3] = {0.0, 0.0, 0.0};
+    printf("# %sprofile along axis %d: bin centre, rho, P_N, P_T%s\n", pre, prof_axis,
+           ik ? " (Irving-Kirkwood contour)" : "");
+    for (int b = 0; b < nb; ++b) {
+        double conf[3];
+        for (int d = 0; d < 3; ++d) {
+            conf[d] = 12.0 * (double)vir[(size_t)d * (size_t)nb + (size_t)b] / 4294967296.0;
+            tot[d] += conf[d];
+        }
+        const double rho = (double)cnt[b] / vbin, ideal = rho / (double)q.beta;
+        printf("%sprofile %.9g %.9g %.9g %.9g\n", pre, -0.5 * len[prof_axis] + (b + 0.5) * width, rho,
+               ideal + conf[prof_axis] / vbin, ideal + 0.5 * (conf[t0] + conf[t1]) / vbin);
+    }
+    const double ideal = (double)fo.particles / (vol * (double)q.beta);
+    printf("%spressure_tensor %.9g %.9g %.9g (N %lld, ordered pairs %lld)\n", pre, ideal + tot[0] / vol,
+           ideal + tot[1] / vol, ideal + tot[2] / vol, (long long)fo.particles, (long long)fo.pairs);
+    printf("%ssurface_tension %.9g (axis %d, two interfaces)\n", pre,
+           0.5 * len[prof_axis] * (tot[prof_axis] - 0.5 * (tot[t0] + tot[t1])) / vol, prof_axis);
+    free(cnt);
+    free(vir);
+}
+
 int main(int argc, char** argv) {
     pmc_params p;
     memset(&p, 0, sizeof(p));
@@ -54,7 +103,7 @@ int main(int argc, char** argv) {
     p.w = 2.5f; p.beta = 0.3f; p.sigma = 0.5f; p.seed = 1234;
     long long atoms = 64;
     int passes = 1000, every = 1, graph = 0, pairobs = 0, widom = 0, sk = 0, gc_moves = 1, gc_every = 1;
-    int prof_axis = -1, prof_bins = 0;
+    int prof_axis = -1, prof_bins = 0, ik_axis = -1, ik_bins = 0;
     float gcmc = 0.0f;
     const char *dump = NULL, *save = NULL, *restart = NULL;
     for (int i = 1; i < argc; ++i) {
@@ -83,6 +132,16 @@ int main(int argc, char** argv) {
             prof_bins = colon ? atoi(colon + 1) : 0;
             if (prof_axis < 0 || prof_axis > 2 || (colon && prof_bins < 1)) {
                 fprintf(stderr, "--profile AXIS[:NBINS]: AXIS 0..2, NBINS >= 1\n");
+                return 2;
+            }
+            ++i;
+        }
+        else if (!strcmp(a, "--profile-ik")) {
+            const char* colon = strchr(v, ':');
+            ik_axis = atoi(v);
+            ik_bins = colon ? atoi(colon + 1) : 0;
+            if (ik_axis < 0 || ik_axis > 2 || (colon && ik_bins < 1)) {
+                fprintf(stderr, "--profile-ik AXIS[:NBINS]: AXIS 0..2, NBINS >= 1\n");
                 return 2;
             }
             ++i;
@@ -243,40 +302,8 @@ int main(int argc, char** argv) {
         free(re);
         free(im);
     }
-    if (prof_axis >= 0) {
-        pmc_params q;
-        pmc_profile_obs fo;
-        if ((rc = pmc_get_params(ctx, &q))) die("pmc_get_params", rc);
-        const int cps[3] = {q.cps_x, q.cps_y, q.cps_z};
-        const int nb = prof_bins ? prof_bins : 4 * cps[prof_axis];
-        uint64_t* cnt = calloc((size_t)nb, sizeof(uint64_t));
-        int64_t* vir = calloc(3 * (size_t)nb, sizeof(int64_t));
-        if (!cnt || !vir) die("calloc", 0);
-        if ((rc = pmc_profiles(ctx, prof_axis, nb, cnt, vir, &fo))) die("pmc_profiles", rc);
-        const double len[3] = {(double)((float)q.cps_x * q.w), (double)((float)q.cps_y * q.w),
-                               (double)((float)q.cps_z * q.w)};
-        const double vol = len[0] * len[1] * len[2], width = len[prof_axis] / nb, vbin = vol / nb;
-        const int t0 = (prof_axis + 1) % 3, t1 = (prof_axis + 2) % 3;
-        double tot[3] = {0.0, 0.0, 0.0};
-        printf("# profile along axis %d: bin centre, rho, P_N, P_T\n", prof_axis);
-        for (int b = 0; b < nb; ++b) {
-            double conf[3];
-            for (int d = 0; d < 3; ++d) {
-                conf[d] = 12.0 * (double)vir[(size_t)d * (size_t)nb + (size_t)b] / 4294967296.0;
-                tot[d] += conf[d];
-            }
-            const double rho = (double)cnt[b] / vbin, ideal = rho / (double)q.beta;
-            printf("profile %.9g %.9g %.9g %.9g\n", -0.5 * len[prof_axis] + (b + 0.5) * width, rho,
-                   ideal + conf[prof_axis] / vbin, ideal + 0.5 * (conf[t0] + conf[t1]) / vbin);
-        }
-        const double ideal = (double)fo.particles / (vol * (double)q.beta);
-        printf("pressure_tensor %.9g %.9g %.9g (N %lld, ordered pairs %lld)\n", ideal + tot[0] / vol, ideal + tot[1] / vol,
-               ideal + tot[2] / vol, (long long)fo.particles, (long long)fo.pairs);
-        printf("surface_tension %.9g (axis %d, two interfaces)\n",
-               0.5 * len[prof_axis] * (tot[prof_axis] - 0.5 * (tot[t0] + tot[t1])) / vol, prof_axis);
-        free(cnt);
-        free(vir);
-    }
+    if (prof_axis >= 0) print_profiles(ctx, prof_axis, prof_bins, 0);
+    if (ik_axis >= 0) print_profiles(ctx, ik_axis, ik_bins, 1);
     pmc_destroy(ctx);
     return 0;
 }

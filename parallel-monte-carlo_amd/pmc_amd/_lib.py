@@ -188,6 +188,7 @@ def lib():
              C.POINTER(ProbeObs))
         _sig(L, "pmc_density_modes", i32, _vp, _vp, i32, _vp, _vp, C.POINTER(SkObs))
         _sig(L, "pmc_profiles", i32, _vp, i32, i32, _vp, _vp, C.POINTER(ProfileObs))
+        _sig(L, "pmc_profiles_ik", i32, _vp, i32, i32, _vp, _vp, C.POINTER(ProfileObs))
         _sig(L, "pmc_exchange_phase", i32, _vp, i32, u32, C.c_float, i32)
         _sig(L, "pmc_exchange_sweep", i32, _vp, u32, C.c_float, i32)
         _sig(L, "pmc_gc_stats_read", i32, _vp, C.POINTER(GcStats), i32)

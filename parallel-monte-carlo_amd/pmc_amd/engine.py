@@ -393,6 +393,11 @@ class PmcContext:
         coordinates: slab ranks and samples add key by key (observables.add_profiles);
         observables.density_profile, pressure_profile, pressure_tensor and surface_tension convert.
 
+        Which contour: this is the Harasima-type (H) assignment.  Its P_T profile, the box tensor and
+        the surface tension are meaningful; its local P_N is NOT flat through an interface.  For the
+        local normal pressure (the flat-P_N check of mechanical equilibrium, P_N - P_T across an
+        interface) use profiles_ik.
+
         Averaging over sweeps: shiftCells translates EVERY coordinate by the sweep plan's d along its
         axis f each sweep, so the whole configuration drifts rigidly through the periodic box and a
         feature (a slab, a film) moves between samples.  Profiles of different sweeps must be
@@ -411,6 +416,32 @@ class PmcContext:
         L = np.array([np.float32(self.cps_x) * w, np.float32(self.cps_y) * w, np.float32(self.cps_z) * w], np.float32)
         return {"count": count, "vir": vir, "virial_fixed": int(out.virial_fixed), "pairs": int(out.pairs),
                 "particles": int(out.particles), "axis": int(axis), "L": L}
+
+    def profiles_ik(self, axis: int = 2, nbins: Optional[int] = None) -> dict:
+        """The profiles of ``profiles`` on the Irving-Kirkwood contour (pmc_profiles_ik,
+        include/pmc_profile_ik.h): the same dict -- count, totals, axis and L are identical -- with,
+        under "vir", every ordered pair's v d_d^2 / r^2 spread over the bins that the straight segment
+        between the two partners crosses along the axis, in proportion to the part of the segment in
+        each bin (exact integer shares of integer position words), and an added "contour": "ik".
+
+        Which contour: P_N from this result is the local normal pressure, constant through a
+        mechanically equilibrated planar interface, and P_N - P_T locates the tension.  The bin sums'
+        totals equal those of ``profiles`` bit for bit, so observables.pressure_tensor and
+        surface_tension give the same numbers from either result; with nbins = 1 the two results are
+        the same.  density_profile, pressure_profile, centre_profile and the alignment advice of
+        ``profiles`` apply unchanged; observables.add_profiles adds IK results to IK results only."""
+        cps_a = (self.cps_x, self.cps_y, self.cps_z)[axis] if axis in (0, 1, 2) else 0
+        nb = 4 * cps_a if nbins is None else int(nbins)
+        count = np.zeros(max(nb, 0), np.uint64)
+        ik = np.zeros((3, max(nb, 0)), np.int64)
+        out = ProfileObs()
+        check("pmc_profiles_ik",
+              lib().pmc_profiles_ik(self._h, int(axis), nb, count.ctypes.data if count.size else None,
+                                    ik.ctypes.data if ik.size else None, C.byref(out)))
+        w = np.float32(self.w)
+        L = np.array([np.float32(self.cps_x) * w, np.float32(self.cps_y) * w, np.float32(self.cps_z) * w], np.float32)
+        return {"count": count, "vir": ik, "virial_fixed": int(out.virial_fixed), "pairs": int(out.pairs),
+                "particles": int(out.particles), "axis": int(axis), "L": L, "contour": "ik"}
 
     def stats(self, reset: bool = False) -> dict:
         s = Stats()

@@ -4,7 +4,8 @@ chemical potential and energy distributions from those of ``PmcContext.probe_ene
 (pmc_probe_energies, include/pmc_probe.h), and the static structure factor S(k) from the density
 modes of ``PmcContext.density_modes`` (pmc_density_modes, include/pmc_sk.h), and the density and
 pressure-tensor profiles and the surface tension from the axis profiles of ``PmcContext.profiles``
-(pmc_profiles, include/pmc_profile.h).
+(pmc_profiles, include/pmc_profile.h) and ``PmcContext.profiles_ik`` (pmc_profiles_ik,
+include/pmc_profile_ik.h).
 
 Pure numpy, no GPU: the sums of several slab contexts are added first (they are exact integers),
 then converted here.  Units are the library's reduced Lennard-Jones units (epsilon = sigma_LJ = 1).
@@ -187,10 +188,13 @@ def add_profiles(a: dict, b: dict) -> dict:
     """Key-wise sum of two profile results over the same axis, bins and box: the slab ranks of one
     sample, or several samples (every entry is an exact integer sum; align samples of different
     sweeps first, see PmcContext.profiles).  Refuses results whose axis, number of bins or box
-    differ."""
+    differ, and results of different contours ("contour": "ik" from PmcContext.profiles_ik; a result
+    without the key is on the H contour of PmcContext.profiles)."""
     if (int(a["axis"]) != int(b["axis"]) or len(a["count"]) != len(b["count"])
             or not np.array_equal(a["L"], b["L"])):
         raise ValueError("add_profiles: results over different axes, bins or box lengths")
+    if a.get("contour", "h") != b.get("contour", "h"):
+        raise ValueError("add_profiles: results of different contours (profiles and profiles_ik)")
     out = dict(a)
     out["count"] = np.asarray(a["count"], np.uint64) + np.asarray(b["count"], np.uint64)
     out["vir"] = np.asarray(a["vir"], np.int64) + np.asarray(b["vir"], np.int64)
@@ -218,9 +222,12 @@ def density_profile(res: dict, samples: int = 1) -> tuple:
 def pressure_profile(res: dict, beta: float, samples: int = 1) -> tuple:
     """(bin centres, P_N, P_T): the ideal part rho_b / beta plus the configurational part
     12 * vir[d][b] / 2^32 / (bin volume); P_N takes d = the axis, P_T the mean of the other two.
-    Each pair is assigned half to each partner's bin (a Harasima-type tangential profile; the normal
-    profile under this assignment is NOT flat through an interface: only its box average and
-    P_N - P_T integrated over the box are contour-independent)."""
+    From a PmcContext.profiles result each pair is assigned half to each partner's bin (a
+    Harasima-type tangential profile; the normal profile under this assignment is NOT flat through an
+    interface: only its box average and P_N - P_T integrated over the box are contour-independent).
+    From a PmcContext.profiles_ik result ("contour": "ik") each pair is spread along the line between
+    the partners: P_N is the local normal pressure, flat through an equilibrated planar interface,
+    and P_N - P_T locates the tension."""
     a, _, _, width, area = _profile_geometry(res)
     centres, rho = density_profile(res, samples)
     conf = 12.0 * np.asarray(res["vir"], np.int64).astype(np.float64) / FIX_SCALE / (area * width * samples)
