@@ -113,7 +113,13 @@ int pmc_get_stream(pmc_ctx* ctx, void** stream);
 /* Use caller-owned device buffers as the context state instead of its own (e.g. torch
  * tensors for RCCL halo exchange).  Each disk buffer holds storage_cells*3*nmax floats in the
  * state layout (pmc_state_layout), each n buffer storage_cells int16; buffer 0 is the current
- * state. */
+ * state.
+ * The slack contract: of a cell's nmax slots only the first n[cell] are particles.  The slots
+ * j >= n[cell] may hold ANYTHING when the caller hands them over (here, in pmc_copy_in and in the
+ * caller buffers of pmc_subsweep / pmc_shift_cells) -- stale coordinates, NaN -- and no result
+ * depends on them: every kernel masks its reads by the counts.  The library in turn leaves them
+ * unspecified after any call that changes the state ("The slack contract";
+ * tests/test_gpu_slack_poison.py). */
 int pmc_attach_state(pmc_ctx* ctx, float* disk0, int16_t* n0, float* disk1, int16_t* n1);
 /* Current state buffers (device pointers, state layout), storage geometry. */
 int pmc_state(pmc_ctx* ctx, float** disk, int16_t** n);
@@ -481,6 +487,8 @@ int pmc_stats_read(pmc_ctx* ctx, pmc_stats* out, int reset);
 int pmc_error_flags(pmc_ctx* ctx, uint32_t* flags, int reset);
 
 /* ---- host mirrors ------------------------------------------------------------------ */
+/* Whole rows both ways, slack included (slots j >= n[cell]: the slack contract at pmc_attach_state --
+ * pmc_copy_in does not sanitise them and nothing reads them). */
 int pmc_copy_out(pmc_ctx* ctx, float* h_disk, int16_t* h_n);
 int pmc_copy_in(pmc_ctx* ctx, const float* h_disk, const int16_t* h_n);
 int pmc_synchronize(pmc_ctx* ctx);

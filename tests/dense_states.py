@@ -100,12 +100,9 @@ def first_sweep_xyz(name, flags=0, count=SWEEPS):
     quirk flags that is the selector's first window for every state; with them (F64: rows full to the
     end, and the quirks accept many more moves) the selector's first window overflows a cell on the
     oracle, so the next clean one is taken."""
-    for s in range(400):
-        if len({pmc_oracle.sweep_plan(SEED, s + k, 2.5, flags)[1] for k in range(count)}) != 3:
-            continue
-        if oracle_state(name, flags=flags).run(s, count) == 0:
-            return s
-    raise RuntimeError(f"dense state {name}: no clean window of {count} sweeps")
+    import row_lengths
+    kw, disk, n = state(name)
+    return row_lengths.window_xyz(("dense", name), kw, disk, n, flags, count)
 
 
 def slab_of(name, nz_local, halo=1, z0=0):

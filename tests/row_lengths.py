@@ -120,15 +120,33 @@ def oracle_of(kw, disk, n):
     return st
 
 
-def first_sweep_xyz(nmax, box=BOX, flags=0, count=SWEEPS, **extra):
-    """The first sweep index whose `count` plans shift along x, y and z and from which the oracle alone
-    runs the mixed state with no cell overflowing (dense_states.first_sweep_xyz's selector)."""
-    for s in range(400):
-        if len({pmc_oracle.sweep_plan(SEED, s + k, W, flags)[1] for k in range(count)}) != 3:
-            continue
-        if oracle_state("mixed", nmax, box, flags=flags, **extra).run(s, count) == 0:
+_windows = {}
+
+
+def window_xyz(key, kw, disk, n, flags=0, count=SWEEPS, clean=True):
+    """The first sweep index whose `count` plans shift along x, y and z and (clean) from which the
+    oracle alone runs the state (kw, disk, n) with no cell overflowing.  The one selector of the state
+    modules (dense_states, slack_poison); cached per process under `key` (None: not cached)."""
+    key = None if key is None else (key, flags, count, clean)
+    if key is None or key not in _windows:
+        kw = dict(kw, flags=flags)
+        for s in range(400):
+            if len({pmc_oracle.sweep_plan(kw.get("seed", SEED), s + k, kw.get("w", W), flags)[1] for k in range(count)}) != 3:
+                continue
+            if not clean or oracle_of(kw, disk, n).run(s, count) == 0:
+                break
+        else:
+            raise RuntimeError(f"state {key}: no clean window of {count} sweeps")
+        if key is None:
             return s
-    raise RuntimeError(f"mixed state nmax={nmax} box={box}: no clean window of {count} sweeps")
+        _windows[key] = s
+    return _windows[key]
+
+
+def first_sweep_xyz(nmax, box=BOX, flags=0, count=SWEEPS, **extra):
+    """window_xyz of the mixed state (dense_states.first_sweep_xyz's selector)."""
+    kw, disk, n = mixed_state(nmax, box, **extra)
+    return window_xyz(("mixed", nmax, box, tuple(sorted(extra.items()))), kw, disk, n, flags, count)
 
 
 def slab(kind, nmax, nz_local, z0=0, halo=1, box=SLAB_BOX):

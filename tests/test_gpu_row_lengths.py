@@ -377,11 +377,13 @@ def _assert_unchanged(before, ctx):
 @pytest.mark.parametrize("kind,nmax", BOTH, ids=BOTH_IDS)
 def test_observables(pmc, kind, nmax):
     """pmc_pair_observables (1 and 37 bins), pmc_probe_energies (both modes, 1 and 64 probes per cell),
-    pmc_density_modes (3 vectors: the folded form; 40: the general form) and pmc_profiles (three axes,
-    1 and 64 bins per cell) against their C references; state, statistics and flags unchanged."""
+    pmc_density_modes (3 vectors: the folded form; 40: the general form), pmc_profiles and
+    pmc_profiles_ik (three axes, 1 and 64 bins per cell) against their C references; state, statistics
+    and flags unchanged."""
     from test_gpu_pairobs import _check as check_pair
     from test_gpu_probe import _check as check_probe
     from test_gpu_profile import _check as check_profile
+    from test_gpu_profile_ik import _check as check_profile_ik
     from test_gpu_sk import _check as check_sk, _vectors
     kw, disk, n = rl.state(kind, nmax)
     g = rl.GuardedContext(pmc, kw, disk, n)
@@ -399,6 +401,7 @@ def test_observables(pmc, kind, nmax):
     for axis in range(3):
         for nbins in (1, 64 * 4):
             assert check_profile(ctx, axis, nbins)["particles"] == total
+            assert check_profile_ik(ctx, axis, nbins)["particles"] == total
     _assert_unchanged(before, ctx)
     g.close()
 
