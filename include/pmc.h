@@ -572,12 +572,14 @@ int pmc_load_snapshot(pmc_ctx* ctx, const char* path, uint32_t* next_sweep);
 /* ---- environment switches read by the library (none is needed in production) ----------
  * Operational:      PMC_IPC_TIMEOUT_S (IPC wait limit, default 60), PMC_LOCAL_GROUP_TIMEOUT_MS,
  *                   PMC_RCCL_LIB (librccl path; SlabDriver sets torch's).
- * Schedule A/B:     PMC_SWEEP_CHAINS, PMC_SLAB_CHAINS, PMC_SLAB_PRIORITY, PMC_SLAB_SPLIT_SHIFT,
+ * Schedule A/B:     PMC_SWEEP_CHAINS, PMC_SLAB_CHAINS, PMC_SLAB_SPLIT_SHIFT,
  *                   PMC_SLAB_DEFER_Z, PMC_SLAB_DIRECT_HALO, PMC_BOUNDARY_FULL, PMC_IPC_FUSED,
  *                   PMC_SMALL, PMC_SMALL_LAUNCH, PMC_DIRECT_CELLS, PMC_FALLBACK_BLOCKS, PMC_SHIFT_RUN,
  *                   PMC_SHIFT_OFF32, PMC_ENERGY_LEGACY, PMC_ENERGY_ROWS_CAP: every
  *                   setting gives the same bits (the GPU tests run the non-default ones); DESIGN.md
- *                   records which were measured and why the default won.
+ *                   records which were measured and why the default won.  PMC_SLAB_PRIORITY=0 (the
+ *                   exchange stream at the default dispatch priority) changes no launch and no
+ *                   dependency; no test sets it.
  * Test hooks:       PMC_SUBSWEEP_CAP (forces the overflow-queue fallback), PMC_FORCE_ADDR64 (64-bit
  *                   addressing below 4 GiB).
  * Timing only:      PMC_XFER_DELAY_US (a one-GPU rehearsal's stand-in for xGMI time per exchange;

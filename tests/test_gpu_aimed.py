@@ -116,6 +116,8 @@ TWO_CELL = {"PMC_SMALL_LAUNCH": "0", "PMC_MIXED_SINGLES": "0"}
 #   mixed-singles    k_subsweep_mixed, which at this size is all single-cell waves (subsweep_wave)
 #   fallback         capacity 64 < K: every cell is queued by the two-cell launch and visited by
 #                    k_subsweep_fallback
+#   fallback-N-*     the same with PMC_FALLBACK_BLOCKS workgroups in the overflow launch instead of 8: one (the
+#                    queue cleared by the workgroup itself, no completion atomics) and 64 (more than queued cells)
 #   addr64*          64-bit addressing in k_subsweep_full and in the two-cell launch
 #   direct           k_subsweep_direct: one cell per wave at the main capacity
 #   energy-*         the per-cell energy kernel alone / taking every queued segment
@@ -123,6 +125,10 @@ VARIANTS = {
     "two-cell": (TWO_CELL, "D1new-A,D1new-B,D2-A,D2-B,D1old,D1wrap,D1oldwrap,D3x-,D3y+,D3z-,D4a,D4b,D4c"),
     "mixed-singles": ({"PMC_SMALL_LAUNCH": "0"}, "D1new-A,D2-B,D3y+,D4c"),
     "fallback": (dict(TWO_CELL, PMC_SUBSWEEP_CAP="64"), "D1new-A,D1new-B,D2-A,D2-B,D3x-,D4c"),
+    "fallback-1-block": (dict(TWO_CELL, PMC_SUBSWEEP_CAP="64", PMC_FALLBACK_BLOCKS="1"),
+                         "D1new-A,D1new-B,D2-A,D2-B,D3x-,D4c"),
+    "fallback-64-blocks": (dict(TWO_CELL, PMC_SUBSWEEP_CAP="64", PMC_FALLBACK_BLOCKS="64"),
+                           "D1new-A,D1new-B,D2-A,D2-B,D3x-,D4c"),
     "addr64": ({"PMC_FORCE_ADDR64": "1"}, "D1new-A,D2-B,D1wrap,D3x-,D4c"),
     "addr64-two-cell": (dict(TWO_CELL, PMC_FORCE_ADDR64="1"), "D1new-A,D1new-B,D2-A,D2-B"),
     "direct": ({"PMC_DIRECT_CELLS": "100000", "PMC_SMALL_LAUNCH": "0"}, "D1new-A,D2-B,D3y+,D4c"),

@@ -137,18 +137,25 @@ def test_single_phases_and_counter_reset(pmc, oracle):
     ctx.close()
 
 
+def _interleaved_reference(st, first, passes, every, k, z=Z):
+    """Oracle sweeps first .. first+passes-1 of the oracle state `st` IN PLACE, a gc_ref sweep after
+    every sweep s with (s + 1) % every == 0; the exchange counters (the oracle's are st.stats)."""
+    want = gc_ref.GcStats()
+    for s in range(first, first + passes):
+        assert st.run(s, 1) == 0
+        if (s + 1) % every == 0:
+            gc_ref.sweep(st.p, st.disk, st.n, s, z, k, want)
+    return want
+
+
 def test_start_gc_equals_interleaved_reference(pmc, oracle):
     """pmc_start_gc over 20 sweeps with gc_every = 2: oracle sweeps interleaved with gc_ref sweeps."""
     ctx = _evolved(pmc, 8, 1500, sweeps=0)
     st = _ref_state(oracle, ctx)
     first, passes, every, k = 1, 20, 2, 3
     r = ctx.run_gc(first, passes, Z, k=k, every=every)
-    want = gc_ref.GcStats()
     e0 = st.energy()
-    for s in range(first, first + passes):
-        assert st.run(s, 1) == 0
-        if (s + 1) % every == 0:
-            gc_ref.sweep(st.p, st.disk, st.n, s, Z, k, want)
+    want = _interleaved_reference(st, first, passes, every, k)
     disk, n = ctx.copy_out()
     assert np.array_equal(n, st.n) and gc_ref.occupied_equal(disk, n, st.disk, st.n, 16)
     assert r["gc"] == want.as_dict() and ctx.gc_stats() == want.as_dict()

@@ -44,14 +44,15 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _run_processes(world, argv, timeout=180, ipc_timeout_s="30"):
-    """Start `world` rank processes of argv, wait; on failure or timeout kill their process groups."""
+def _run_processes(world, argv, timeout=180, ipc_timeout_s="30", env=None):
+    """Start `world` rank processes of argv, wait; on failure or timeout kill their process groups.
+    env: further environment values of the ranks (tests/test_gpu_ipc_shapes.py: PMC_IPC_FUSED)."""
     port = str(_free_port())
     procs = []
     for r in range(world):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=port, PMC_IPC_TIMEOUT_S=ipc_timeout_s)
-        procs.append(subprocess.Popen([sys.executable] + argv, env=env, start_new_session=True,
+        rank_env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                        MASTER_PORT=port, PMC_IPC_TIMEOUT_S=ipc_timeout_s, **(env or {}))
+        procs.append(subprocess.Popen([sys.executable] + argv, env=rank_env, start_new_session=True,
                                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     outs = [None] * world
     try:

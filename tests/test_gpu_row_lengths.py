@@ -8,8 +8,8 @@ property relied on here).  Every context runs on caller-owned state buffers with
 after each of them (row_lengths.GuardedContext, pmc_attach_state), the last cell's record flush
 against the sentinel.  Tolerance: none -- slots, counts, counters, flags and energies are bit-equal.
 
-Not covered: a one-process rehearsal of the IPC halo transport (tests/test_gpu_multirank.py has none to
-call)."""
+The IPC halo transport at these row lengths, its one-rank rehearsal included, runs as rank processes:
+tests/test_gpu_ipc_shapes.py (test_ipc_one_rank_rehearsal)."""
 import os
 import subprocess
 import sys
