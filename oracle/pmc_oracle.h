@@ -7,9 +7,10 @@
  * independent cells of one colour) of the reference algorithm as specified in SURVEY.md
  * Appendix A ("corrected mode"); each function cites the reference lines it follows.
  *
- * Parity pinning: see oracle/README.md and DESIGN.md section "Oracle".  The reference cannot
- * be built here (CUDA + cuRAND absent; building it would need stand-in headers, which this
- * project does not write), so the oracle is pinned by the reference's own data file
+ * Parity pinning: see DESIGN.md section "Oracle and parity".  The subsweep and both copies of
+ * shiftCells are pinned by the reference's own subsweep.h / shiftCells.h, compiled for the host
+ * behind a CUDA shim and fed this project's random numbers (oracle/ref_harness,
+ * tests/test_reference_fixtures.py); init_r, assign and the energy by the reference's own data file
  * CUDA-Parallel-MC/CUDA-Parallel-MC/dumpR3.txt (lattice + energy function), by the lattice
  * energies derived from its definitions, by published Philox KATs and by statistical known
  * answers of <E> from an independent textbook Metropolis code (tools/textbook_mc.c,
