@@ -433,6 +433,35 @@ int pmc_profiles(pmc_ctx* ctx, int axis, int nbins, uint64_t* h_count, int64_t* 
  * surface tension are the same.  Arguments, PMC_ERR_ARG cases, stream, synchronisation and what is
  * left unchanged: as for pmc_profiles.  Additive over slab ranks without a reduction. */
 int pmc_profiles_ik(pmc_ctx* ctx, int axis, int nbins, uint64_t* h_count, int64_t* h_ik, pmc_profile_obs* out);
+/* Cluster analysis of the owned cells' particles, defined bit for bit in pmc_cluster.h: the degree
+ * deg(i) of every particle (partners with r <= r_bond, pmc_pairobs.h's walk), the core particles
+ * (deg >= min_neighbours; 0: every particle, plain Stillinger clusters; > 0: the ten Wolde-Frenkel
+ * liquid-like criterion) and the clusters: the connected components of the core particles under
+ * "bonded in either direction".  The reference has no such observable.  All pointers are HOST
+ * pointers.  h_size[nbins]: bin s - 1 counts the clusters of size s, the last bin the sizes >= nbins.
+ * h_deg[PMC_CLUSTER_DEG_BINS = 128]: bin d counts the owned particles of degree d, the last bin the
+ * degrees >= 127.  h_label (may be NULL): storage_cells * nmax int32 in slot order (cell c, slot s at
+ * c * nmax + s, which is also the particle's id): the cluster label -- the smallest id in the
+ * cluster -- of a core particle, -1 for a particle that is not core and for an empty slot.
+ * PMC_ERR_ARG (outputs untouched) for a null h_size, h_deg or out, r_bond not finite, <= 0 or > w,
+ * min_neighbours outside 0..127, nbins outside 1..4096, storage_cells * nmax >= 2^31, and for any
+ * slab context (halo != 0): a cluster that crosses a slab face is not additive over ranks, and
+ * merging labels across ranks is not implemented.  Runs on the context stream and synchronises;
+ * state, statistics, exchange counters, error flags and the energy are left unchanged.  Device
+ * scratch (10 bytes per slot) is allocated on the first call and freed by pmc_destroy; a failed
+ * allocation returns PMC_ERR_HIP and leaves the context usable. */
+typedef struct pmc_cluster_obs {
+    int64_t particles;      /* particles in owned cells */
+    int64_t core;           /* core particles: deg >= min_neighbours */
+    int64_t bonds;          /* ordered pairs with r2 <= rb2 over all particles (the sum of the degrees) */
+    int64_t core_bonds;     /* ordered pairs with r2 <= rb2 and both ends core */
+    int64_t clusters;       /* clusters (components of the core particles) */
+    int64_t largest;        /* size of the largest cluster (0 without clusters) */
+    int64_t largest_label;  /* the smallest label among the clusters of that size (-1 without clusters) */
+    int64_t sum_s2;         /* sum over clusters of size^2 */
+} pmc_cluster_obs;
+int pmc_clusters(pmc_ctx* ctx, float r_bond, int min_neighbours, int nbins, uint64_t* h_size, uint64_t* h_deg,
+                 int32_t* h_label, pmc_cluster_obs* out);
 /* ---- grand-canonical exchange moves (mu V T) ------------------------------------------------
  * Insertions and deletions as a further kind of colour phase, defined bit for bit in pmc_gc.h: every
  * owned cell of the colour runs k_per_cell (1..64) attempts in order on its own particle list, each

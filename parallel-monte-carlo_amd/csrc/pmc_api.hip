@@ -13,6 +13,7 @@
 
 #include "pmc_ctx.h"
 #include "../../include/pmc_pairobs.h"
+#include "../../include/pmc_cluster.h"
 #include "../../include/pmc_probe.h"
 #include "../../include/pmc_gc.h"
 #include "../../include/pmc_sk.h"
@@ -22,6 +23,7 @@ using namespace pmc;
 using namespace pmc_sched;
 
 static_assert(kPairObsMaxBins == PMC_PAIROBS_MAX_BINS, "pair observables: bin cap");
+static_assert(kClusterMaxBins == PMC_CLUSTER_MAX_BINS && kClusterDegBins == PMC_CLUSTER_DEG_BINS, "cluster analysis: bin caps");
 static_assert(kProbeMaxBins == PMC_PROBE_MAX_BINS, "test-particle energies: bin cap");
 static_assert(kSkMaxK == PMC_SK_MAX_K, "density modes: vector cap");
 static_assert(kGcCounters == PMC_GC_COUNTERS && sizeof(pmc_gc_stats) == 8 * PMC_GC_COUNTERS, "exchange moves: counters");
@@ -312,6 +314,8 @@ void pmc_destroy(pmc_ctx* c) {
     if (c->sk_acc) (void)hipFree(c->sk_acc);
     if (c->prof_acc) (void)hipFree(c->prof_acc);
     if (c->gc_acc) (void)hipFree(c->gc_acc);
+    for (void* m : {(void*)c->cl_parent, (void*)c->cl_size, (void*)c->cl_deg, (void*)c->cl_acc})
+        if (m) (void)hipFree(m);
     if (c->flags) (void)hipFree(c->flags);
     if (c->ovf) (void)hipFree(c->ovf);
     if (c->ovf_aux) (void)hipFree(c->ovf_aux);
@@ -702,6 +706,67 @@ int pmc_pair_observables(pmc_ctx* c, float r_max, int nbins, uint64_t* h_hist, p
     out->pairs = (int64_t)s[1];
     out->particles = (int64_t)s[2];
     for (int b = 0; b < nbins; ++b) h_hist[b] = (uint64_t)s[(size_t)kPairObsHead + (size_t)b];
+    return PMC_OK;
+}
+
+int pmc_clusters(pmc_ctx* c, float r_bond, int min_neighbours, int nbins, uint64_t* h_size, uint64_t* h_deg,
+                 int32_t* h_label, pmc_cluster_obs* out) {
+    if (!c || !h_size || !h_deg || !out) return fail(PMC_ERR_ARG, "bad argument");
+    if (c->P.halo != 0)
+        return fail(PMC_ERR_ARG, "pmc_clusters: whole-box contexts only (halo == 0): a cluster that crosses a slab face "
+                                 "is not additive over ranks, and merging labels across ranks is not implemented");
+    if (!std::isfinite(r_bond) || !(r_bond > 0.0f) || r_bond > c->P.w)
+        return fail(PMC_ERR_ARG, "pmc_clusters: r_bond must be finite, > 0 and <= w");
+    if (min_neighbours < 0 || min_neighbours > PMC_CLUSTER_MAX_MIN_NEIGHBOURS)
+        return fail(PMC_ERR_ARG, "pmc_clusters: min_neighbours must be in 0..127");
+    if (nbins < 1 || nbins > PMC_CLUSTER_MAX_BINS) return fail(PMC_ERR_ARG, "pmc_clusters: nbins must be in 1..4096");
+    const int64_t slots64 = c->cells * (int64_t)c->P.nmax;
+    if (slots64 >= ((int64_t)1 << 31)) return fail(PMC_ERR_ARG, "pmc_clusters: storage_cells * nmax must be below 2^31");
+    const size_t slots = (size_t)slots64;
+    if (int rj = slab_join(c)) return rj;
+    if (!c->cl_acc) {
+        // all four or none: a failed allocation leaves the context as it was
+        hipError_t e = hipMalloc(&c->cl_parent, sizeof(int) * slots);
+        if (e == hipSuccess) e = hipMalloc(&c->cl_size, sizeof(unsigned) * slots);
+        if (e == hipSuccess) e = hipMalloc(&c->cl_deg, sizeof(uint16_t) * slots);
+        if (e == hipSuccess) e = hipMalloc(&c->cl_acc, sizeof(unsigned long long) * cluster_acc_words(kClusterMaxBins));
+        if (e != hipSuccess) {
+            for (void* m : {(void*)c->cl_parent, (void*)c->cl_size, (void*)c->cl_deg, (void*)c->cl_acc})
+                if (m) (void)hipFree(m);
+            c->cl_parent = nullptr;
+            c->cl_size = nullptr;
+            c->cl_deg = nullptr;
+            c->cl_acc = nullptr;
+            (void)hipGetLastError();   // the context stays usable
+            return hip_fail(e, "pmc_clusters: scratch allocation");
+        }
+    }
+    const size_t words = cluster_acc_words(nbins);
+    PMC_HIP(hipMemsetAsync(c->cl_parent, 0xFF, sizeof(int) * slots, c->stream));
+    PMC_HIP(hipMemsetAsync(c->cl_size, 0, sizeof(unsigned) * slots, c->stream));
+    PMC_HIP(hipMemsetAsync(c->cl_acc, 0, sizeof(unsigned long long) * words, c->stream));
+    hipError_t e = launch_clusters(c->G, c->disk[c->cur], c->n[c->cur], pmc_cutoff_r2(r_bond), min_neighbours, nbins,
+                                   c->cl_parent, c->cl_size, c->cl_deg, c->cl_acc, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "cluster analysis launch");
+    std::vector<unsigned long long> h(words);
+    PMC_HIP(hipMemcpyAsync(h.data(), c->cl_acc, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, c->stream));
+    if (h_label) PMC_HIP(hipMemcpyAsync(h_label, c->cl_parent, sizeof(int32_t) * slots, hipMemcpyDeviceToHost, c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    constexpr size_t per = (size_t)kClusterHead + kClusterDegBins;
+    std::vector<unsigned long long> s(per, 0ull);
+    for (int k = 0; k < kClusterCopies; ++k)
+        for (size_t i = 0; i < per; ++i) s[i] += h[(size_t)k * per + i];
+    const unsigned long long* tail = h.data() + (size_t)kClusterCopies * per;
+    out->bonds = (int64_t)s[0];
+    out->particles = (int64_t)s[1];
+    out->core = (int64_t)s[2];
+    out->core_bonds = (int64_t)s[3];
+    out->clusters = (int64_t)tail[0];
+    out->sum_s2 = (int64_t)tail[1];
+    out->largest = (int64_t)(tail[2] >> 32);
+    out->largest_label = tail[0] ? (int64_t)(0x7FFFFFFFu - (uint32_t)(tail[2] & 0xFFFFFFFFull)) : -1;
+    for (int b = 0; b < PMC_CLUSTER_DEG_BINS; ++b) h_deg[b] = (uint64_t)s[(size_t)kClusterHead + (size_t)b];
+    for (int b = 0; b < nbins; ++b) h_size[b] = (uint64_t)tail[(size_t)kClusterTail + (size_t)b];
     return PMC_OK;
 }
 

@@ -32,6 +32,11 @@ struct pmc_ctx {
     int sk_cap = 0;                            // vectors sk_acc has room for
     unsigned long long* prof_acc = nullptr;    // axis profiles: accumulator copies (grown with nbins)
     int prof_cap = 0;                          // bins prof_acc has room for
+    // cluster analysis: per-slot scratch and the accumulators (allocated together on first use)
+    int* cl_parent = nullptr;                  // storage_cells * nmax: union-find parent, then the labels
+    unsigned* cl_size = nullptr;               // storage_cells * nmax: particles per root
+    uint16_t* cl_deg = nullptr;                // storage_cells * nmax: degrees
+    unsigned long long* cl_acc = nullptr;      // cluster_acc_words(kClusterMaxBins)
     unsigned long long* gc_acc = nullptr;      // exchange moves: accumulator copies (allocated on first use; kept until reset)
     uint32_t* flags = nullptr;
     int* ovf = nullptr;                   // subsweep overflow queue (1 + cells per colour)

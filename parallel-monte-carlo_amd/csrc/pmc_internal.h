@@ -209,6 +209,26 @@ hipError_t launch_profile(const DevGeom& g, const float* disk, const int16_t* n,
 constexpr int kProfIkWin = 200;      // bins of a wave's LDS window (a cell's three-cell span: at most 3 * 64 + 4)
 hipError_t launch_profile_ik(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int axis,
                              int nbins, hipStream_t st);
+// cluster analysis (k_cluster_walk, k_cluster_flatten, k_cluster_count; pmc_cluster.h) of a whole-box
+// context (halo == 0) with slots = cells * nmax < 2^31.  parent (int32) and size (u32) hold one entry
+// per slot, set to -1 and 0 on st before the call; deg (u16) one per slot, written before it is read.
+// acc, zeroed on st before the call: kClusterCopies accumulator copies of kClusterHead +
+// kClusterDegBins counters each ([0] ordered bonds, [1] owned particles, [2] core particles, [3]
+// ordered bonds between core particles, then the degree histogram) the host sums, then one tail of
+// kClusterTail + nbins counters ([0] clusters, [1] sum of size^2, [2] the maximum of size << 32 |
+// 0x7FFFFFFF - label, then the size histogram).  After the call parent holds the labels.
+constexpr int kClusterCopies = 32;
+constexpr int kClusterHead = 4;
+constexpr int kClusterTail = 3;
+constexpr int kClusterDegBins = 128;   // PMC_CLUSTER_DEG_BINS
+constexpr int kClusterMaxBins = 4096;  // PMC_CLUSTER_MAX_BINS
+static_assert((kClusterCopies & (kClusterCopies - 1)) == 0, "accumulator copies: a power of two");
+constexpr size_t cluster_acc_words(int nbins) {
+    return (size_t)kClusterCopies * (kClusterHead + kClusterDegBins) + kClusterTail + (size_t)nbins;
+}
+hipError_t launch_clusters(const DevGeom& g, const float* disk, const int16_t* n, float rb2, int min_neighbours,
+                           int nbins, int* parent, unsigned* size, uint16_t* deg, unsigned long long* acc,
+                           hipStream_t st);
 // the cells of one colour of one plane: mode 0 plane -> packed buffer, 1 packed -> plane,
 // 2 plane -> plane; (cps_x/2)*(cps_y/2)*3*nmax floats
 hipError_t launch_colour_rows(const DevGeom& g, const float* src, float* dst, int colour, int mode, hipStream_t st);

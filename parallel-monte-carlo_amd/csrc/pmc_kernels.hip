@@ -26,6 +26,7 @@
 #include "pmc_internal.h"
 #include "../../include/pmc_detmath.h"
 #include "../../include/pmc_pairobs.h"
+#include "../../include/pmc_cluster.h"
 #include "../../include/pmc_probe.h"
 #include "../../include/pmc_gc.h"
 #include "../../include/pmc_sk.h"
@@ -2754,6 +2755,342 @@ __global__ __launch_bounds__(kWave) void k_pairobs(DevGeom g, const float* __res
 }
 
 // ------------------------------------------------------------------------------------------
+// cluster analysis (include/pmc_cluster.h): degrees, core particles and the connected components of
+// the core particles under "bonded in either direction", in four launches on one stream.
+//
+// k_cluster_walk<.., false> (degree) and <.., true> (link) are k_pairobs' per-cell form: the same
+// stencil (pairobs_stencil), the same staging (rows of 8 slots, chunks for the fuller cells, own cell
+// first, the pmc_box_d2 filter -- conservative for r_bond <= w -- and the 27 * nmax LDS capacity),
+// the same fixed grid of waves over runs of kPairObsRun cells.  Degree: lane i keeps the degree of
+// own particle i (ballot / popcount per partner block), then writes deg[id] and the initial
+// parent[id] (id if core, the memset's -1 otherwise) and bins the degree in the wave's LDS
+// histogram.  Link: every staged particle carries a tag beside its position (its id if it is core,
+// else -1; deg[] is final by then); on every directed hit between two core particles the hit's lane
+// unites the two ids.
+//
+// The union is lock-free: both ids are followed to their roots (cluster_find), and the LARGER root
+// is hooked under the smaller one with atomicCAS(&parent[hi], hi, lo).  A failed CAS means another
+// wave hooked `hi` first; the loop goes on from the value the CAS returned.  parent[x] <= x always,
+// and every store (a hook, a path-halving store, the flatten store) writes a smaller proper
+// ancestor, so every find ends, no wave waits for a value another wave must write, and at the end
+// the root of a component is its smallest id.  parent[] is read with relaxed agent-scope atomic
+// loads and written with agent-scope atomics only; a stale read yields an ancestor (or the node
+// itself), which the CAS corrects.
+//
+// k_cluster_flatten: one thread per slot follows its particle to the root, stores it as the label
+// and adds 1 to size[root], one atomic per distinct root of a wave.  k_cluster_count: one thread per
+// slot; a root (parent[id] == id) bins its size in the block's LDS histogram and joins the block's
+// cluster count, sum of squares and (size, smallest label) maximum.  Integers only, independent of
+// every order: equal to tests/cluster_ref.c bit for bit.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int cluster_ld(const int* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// root of x, halving the path on the way (each store replaces a parent by the grandparent)
+__device__ __forceinline__ int cluster_find(int* __restrict__ parent, int x) {
+    int p = cluster_ld(parent + x);
+    while (p != x) {
+        const int gp = cluster_ld(parent + p);
+        if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = p;
+        p = gp;
+    }
+    return x;
+}
+
+__device__ __forceinline__ void cluster_unite(int* __restrict__ parent, int a, int b) {
+    for (;;) {
+        a = cluster_find(parent, a);
+        b = cluster_find(parent, b);
+        if (a == b) return;
+        const int hi = a > b ? a : b, lo = a > b ? b : a;
+        const int old = atomicCAS(parent + hi, hi, lo);
+        if (old == hi) return;
+        a = old;   // hi was hooked meanwhile: go on from its new parent (same tree as hi)
+        b = lo;
+    }
+}
+
+template <int NSLOT, bool OFF32, bool LINK>
+__global__ __launch_bounds__(kWave) void k_cluster_walk(DevGeom g, const float* __restrict__ disk,
+                                                        const int16_t* __restrict__ ncnt,
+                                                        unsigned long long* __restrict__ acc, uint32_t total_cells,
+                                                        float rb2, int min_nb, int* __restrict__ parent,
+                                                        uint16_t* __restrict__ deg) {
+    extern __shared__ __attribute__((aligned(16))) float csm[];
+    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
+    constexpr int CPP = kWave / HS;    // cells per staging pass
+    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
+    using DA = DiskAddr<OFF32>;
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int cap = 27 * nm;
+    float* ex_ = csm;
+    float* ey_ = csm + cap;
+    float* ez_ = csm + 2 * cap;
+    int* et_ = (int*)(csm + 3 * cap);              // link: tag of a staged particle (id if core, else -1)
+    int* inv_l = et_ + (LINK ? cap : 0);           // list entry -> stencil lane (32 ints)
+    unsigned* hist = (unsigned*)(inv_l + 32);      // degree: kClusterDegBins counters of this wave
+    const int p = lane % HS;
+    const int ee = lane / HS;
+    unsigned long long n_pairs = 0, n_part = 0, n_core = 0;    // wave-uniform
+    if constexpr (!LINK)
+        for (int b = lane; b < kClusterDegBins; b += kWave) hist[b] = 0u;
+    if (lane < 32) inv_l[lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+
+    auto tag_of = [&](int id) {
+        if constexpr (LINK) return (int)deg[id] >= min_nb ? id : -1;
+        else return 0;
+    };
+
+    // rows of the cell in flight (k_pairobs' issue_rows): slots [0, HS) of its occupied stencil cells
+    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
+    int vt[NPMAX];
+    bool vact[NPMAX];
+    int ncells = 0;
+    auto issue_rows = [&](const PairObsStencil& st) {
+        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
+        ncells = __popcll(mo);
+        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int q = 0; q < NPMAX; ++q) {
+            const int e = q * CPP + ee;
+            const int src = inv_l[e < ncells ? e : 0];
+            const int c_cnt = __shfl(st.cnt, src);
+            const int c_idx = __shfl(st.kc, src);
+            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
+            vact[q] = e < ncells && p < c_cnt;
+            vx[q] = vy[q] = vz[q] = 0.0f;
+            vt[q] = -1;
+            if (vact[q]) {
+                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
+                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
+                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
+                vy[q] = vy[q] + isy;
+                vz[q] = vz[q] + isz;
+                vt[q] = tag_of(c_idx * nm + p);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
+    };
+
+    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
+    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
+        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
+        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
+        issue_rows(cur);
+        PairObsStencil nxt = cur;
+        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
+        for (int c = 0; c < ncl; ++c) {
+            // ---- stage cell c (k_pairobs' staging): own particles first, then the filtered partners
+            float blo[3], bhi[3];
+            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
+            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
+            int S = 0;
+            auto put = [&](bool act, float ux, float uy, float uz, int ut) {
+                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+                if (act) {
+                    const int dst = S + mbcnt64(am);
+                    ex_[dst] = ux;
+                    ey_[dst] = uy;
+                    ez_[dst] = uz;
+                    if constexpr (LINK) et_[dst] = ut;
+                }
+                S += __popcll(am);
+            };
+            // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles
+            auto chunks = [&](unsigned long long mg, bool filter) {
+                if constexpr (NSLOT > HS) {
+                    for (int s0 = HS; s0 < nm; s0 += HS) {
+                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
+                        while (ov) {
+                            int ks = 0, nc = 0;
+                            for (; nc < CPP && ov; ++nc) {
+                                const int kb = (int)__builtin_ctzll(ov);
+                                ov &= ov - 1ull;
+                                ks = ee == nc ? kb : ks;
+                            }
+                            const int c_cnt = __shfl(cur.cnt, ks);
+                            const int c_idx = __shfl(cur.kc, ks);
+                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
+                            const int ps = s0 + p;
+                            const bool act = ee < nc && ps < c_cnt;
+                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+                            int ut = -1;
+                            if (act) {
+                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
+                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+                                ux = ux + isx;
+                                uy = uy + isy;
+                                uz = uz + isz;
+                                ut = tag_of(c_idx * nm + ps);
+                            }
+                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz, ut);
+                        }
+                    }
+                }
+            };
+            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
+            const int id0 = __builtin_amdgcn_readfirstlane(cur.kc) * nm;  // id of the own cell's slot 0
+            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
+            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0], vt[0]);      // own slots [0, HS)
+            chunks(1ull, false);                                          // own slots [HS, n)
+#pragma unroll
+            for (int q = 0; q < NPMAX; ++q) {
+                const int e = q * CPP + ee;
+                if (q * CPP < ncells)
+                    put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q], vt[q]);
+            }
+            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            // ---- the next cell's rows go out now and arrive while this cell's pairs run
+            if (c + 1 < ncl) {
+                cur = nxt;
+                issue_rows(cur);
+                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
+            }
+            n_part += (unsigned long long)n_own;
+            if (n_own == 0) continue;
+            // ---- ordered pairs (i, j): lane j holds staged partner j (blocks of 64), own particle
+            //      i (staged first, in slot order: lane i of block 0) broadcast by readlane; j == i skipped
+            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+            int ot = -1;                                                   // link: the own particles' tags
+            if constexpr (LINK) ot = et_[lane];
+            int mydeg = 0;                                                 // degree: lane i, own particle i
+            auto block = [&](int jb, auto first_c) {
+                constexpr bool kFirst = decltype(first_c)::value;
+                const int j = jb + lane;
+                const bool vj = j < S;
+                const int jj = vj ? j : 0;
+                float xj = ox, yj = oy, zj = oz;
+                int tj = ot;
+                if constexpr (!kFirst) {
+                    xj = ex_[jj];
+                    yj = ey_[jj];
+                    zj = ez_[jj];
+                    if constexpr (LINK) tj = et_[jj];
+                }
+                const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
+                for (int i = 0; i < n_own; ++i) {
+                    int ti = 0;
+                    if constexpr (LINK) {
+                        ti = __builtin_amdgcn_readlane(ot, i);
+                        if (ti < 0) continue;   // wave-uniform: a particle that is not core has no edges
+                    }
+                    const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+                    const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+                    const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+                    const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
+                    unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rb2) & vm;
+                    if constexpr (kFirst) im &= ~(1ull << i);
+                    if constexpr (LINK) {
+                        const bool hit = ((im >> lane) & 1ull) && tj >= 0;
+                        n_pairs += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(hit));
+                        if (hit) cluster_unite(parent, ti, tj);
+                    } else {
+                        const int k = __popcll(im);
+                        n_pairs += (unsigned long long)k;
+                        mydeg += lane == i ? k : 0;
+                    }
+                }
+            };
+            block(0, std::true_type{});
+            for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
+            if constexpr (!LINK) {
+                const bool own = lane < n_own;
+                const bool core = own && mydeg >= min_nb;
+                if (own) {
+                    deg[id0 + lane] = (uint16_t)mydeg;   // at most 27 * 64 - 1
+                    if (core) parent[id0 + lane] = id0 + lane;
+                    (void)__hip_atomic_fetch_add(&hist[pmc_cluster_deg_bin(mydeg)], 1u, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                n_core += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(core));
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+        }
+    }
+    // ---- flush: degree [bonds, particles, core, -, hdeg[]]; link [-, -, -, core_bonds]
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kClusterCopies - 1)) * (size_t)(kClusterHead + kClusterDegBins);
+    if constexpr (LINK) {
+        if (lane == 0 && n_pairs != 0) atomicAdd(&mine[3], n_pairs);
+    } else {
+        const unsigned long long head3 = lane == 0 ? n_pairs : (lane == 1 ? n_part : n_core);
+        if (lane < 3 && head3 != 0) atomicAdd(&mine[lane], head3);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        for (int b = lane; b < kClusterDegBins; b += kWave) {
+            const unsigned h = hist[b];
+            if (h) atomicAdd(&mine[kClusterHead + b], (unsigned long long)h);
+        }
+    }
+}
+
+// labels and sizes: parent[id] := root of id for every core particle (the others and the empty slots
+// keep the memset's -1), size[root] += 1 with one atomic per distinct root of a wave
+__global__ __launch_bounds__(256) void k_cluster_flatten(int* __restrict__ parent, unsigned* __restrict__ size,
+                                                         uint32_t slots) {
+    const uint32_t nthreads = gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    // whole waves leave together: the bound is rounded up to the wave
+    const uint32_t lim = (slots + (uint32_t)kWave - 1u) / (uint32_t)kWave * (uint32_t)kWave;
+    for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < lim; id += nthreads) {
+        int r = -1;
+        if (id < slots && cluster_ld(parent + id) >= 0) {
+            r = (int)id;
+            for (int q = cluster_ld(parent + r); q != r; q = cluster_ld(parent + r)) r = q;
+            if (r != (int)id) __hip_atomic_store(parent + id, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        unsigned long long todo = __builtin_amdgcn_ballot_w64(r >= 0);
+        while (todo) {
+            const int r0 = __shfl(r, (int)__builtin_ctzll(todo));
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(r == r0);
+            if (lane == (int)__builtin_ctzll(m)) atomicAdd(&size[r0], (unsigned)__popcll(m));
+            todo &= ~m;
+        }
+    }
+}
+
+// tail: [0] clusters, [1] sum of size^2, [2] max of (size << 32 | 0x7FFFFFFF - label), then hsize[nbins]
+__global__ __launch_bounds__(256) void k_cluster_count(const int* __restrict__ parent,
+                                                       const unsigned* __restrict__ size, uint32_t slots,
+                                                       unsigned long long* __restrict__ tail, int nbins) {
+    extern __shared__ unsigned hsz[];
+    for (int b = threadIdx.x; b < nbins; b += blockDim.x) hsz[b] = 0u;
+    __syncthreads();
+    const uint32_t nthreads = gridDim.x * blockDim.x;
+    unsigned long long cnt = 0, s2 = 0, key = 0;
+    for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < slots; id += nthreads) {
+        if (parent[id] != (int)id) continue;
+        const unsigned long long s = size[id];
+        atomicAdd(&hsz[pmc_cluster_size_bin((int64_t)s, nbins)], 1u);
+        ++cnt;
+        s2 += s * s;
+        const unsigned long long k = (s << 32) | (unsigned long long)(0x7FFFFFFFu - id);
+        key = k > key ? k : key;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_xor(cnt, o);
+        s2 += __shfl_xor(s2, o);
+        const unsigned long long k = __shfl_xor(key, o);
+        key = k > key ? k : key;
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0 && cnt != 0) {
+        atomicAdd(&tail[0], cnt);
+        atomicAdd(&tail[1], s2);
+        atomicMax(&tail[2], key);
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < nbins; b += blockDim.x) {
+        const unsigned h = hsz[b];
+        if (h) atomicAdd(&tail[kClusterTail + b], (unsigned long long)h);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // test-particle energies (include/pmc_probe.h): per owned cell, kpc Widom insertions at Philox
 // positions (PMC_PROBE_INSERT) or the cell's own particles with their own slot skipped
 // (PMC_PROBE_REAL), each against the cell's 27-cell stencil.  k_pairobs' per-cell form: the same
@@ -4756,6 +5093,37 @@ hipError_t launch_pairobs(const DevGeom& g, const float* disk, const int16_t* n,
         hipLaunchKernelGGL((k_pairobs<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, rmax2, bscale,
                            nbins);
     });
+    return hipGetLastError();
+}
+
+// The four launches of the cluster analysis (pmc_internal.h states the buffers).  launch_pairobs'
+// fixed grid for the two walks: 6.9 KiB of LDS per wave at nmax 16 for the link walk (positions and
+// tags), 5.8 KiB for the degree walk.  Flatten and count: one thread per slot, at most 4096 blocks.
+hipError_t launch_clusters(const DevGeom& g, const float* disk, const int16_t* n, float rb2, int min_neighbours,
+                           int nbins, int* parent, unsigned* size, uint16_t* deg, unsigned long long* acc,
+                           hipStream_t st) {
+    if (nbins < 1 || nbins > kClusterMaxBins || g.halo != 0 || min_neighbours < 0) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells = storage cells
+    const int64_t slots = total * g.nmax;
+    if (slots >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
+    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
+    const size_t lds_deg = sizeof(float) * (3 * 27 * (size_t)g.nmax + 32 + kClusterDegBins);
+    const size_t lds_link = sizeof(float) * (4 * 27 * (size_t)g.nmax + 32);
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
+    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
+        hipLaunchKernelGGL((k_cluster_walk<NS, O, false>), grid, block, lds_deg, st, g, disk, n, acc, (uint32_t)total,
+                           rb2, min_neighbours, parent, deg);
+        hipLaunchKernelGGL((k_cluster_walk<NS, O, true>), grid, block, lds_link, st, g, disk, n, acc, (uint32_t)total,
+                           rb2, min_neighbours, parent, deg);
+    });
+    const int64_t nb = (slots + 255) / 256;
+    const dim3 grid_s((unsigned)(nb < 4096 ? nb : 4096)), block_s(256);
+    hipLaunchKernelGGL(k_cluster_flatten, grid_s, block_s, 0, st, parent, size, (uint32_t)slots);
+    hipLaunchKernelGGL(k_cluster_count, grid_s, block_s, sizeof(unsigned) * (size_t)nbins, st, parent, size,
+                       (uint32_t)slots, acc + (size_t)kClusterCopies * (kClusterHead + kClusterDegBins), nbins);
     return hipGetLastError();
 }
 

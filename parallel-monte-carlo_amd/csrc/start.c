@@ -6,7 +6,7 @@
  *         [--sigma 0.5] [--w 2.5] [--seed 1234] [--every 1] [--graph]
  *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS] [--widom K]
  *         [--sk HMAX] [--profile AXIS[:NBINS]] [--profile-ik AXIS[:NBINS]]
- *         [--gcmc Z [--gc-moves K] [--gc-every M]]
+ *         [--gcmc Z [--gc-moves K] [--gc-every M]] [--clusters RB[:MINNB]]
  *
  * --dump writes create_dump frames (kernel.cu:510-536; the reference's VISUALISATION path) of the
  * initial state and after every --every sweeps; --save writes a PMCSNAP1 snapshot at the end;
@@ -35,6 +35,12 @@
  * after every sweep s with (s + 1) % M == 0 (--gc-every, default 1) one exchange sweep of K insert /
  * delete attempts per cell and colour phase (--gc-moves, default 1).  Every report line then also
  * prints the particle number N and the interval's insert and delete acceptance; not with --graph.
+ *
+ * --clusters RB[:MINNB] runs the cluster analysis (pmc_clusters: bond length RB <= w, a core particle
+ * has at least MINNB bonds, default 0 = plain Stillinger clusters) with every report: one `clusters`
+ * line with the sweep index, the number of clusters, the largest one's size, the weight-average size
+ * sum s^2 / sum s and the core ("liquid-like") fraction, then the integers behind them; at the end the
+ * final state's size table, one `cluster_size` line per occupied bin of 64 (the last: sizes >= 64).
  *
  * Prints "step: energy" lines like kernel.cu:643,695 (energy from the cell-list sum every
  * --every sweeps) and a final summary with acceptance ratio and trial-moves/s.  Compile-time
@@ -96,6 +102,28 @@ static void print_profiles(pmc_ctx* ctx, int prof_axis, int prof_bins, int ik) {
     free(vir);
 }
 
+/* --clusters: the report line of the current state (table 0) or its size table (table 1) */
+static void print_clusters(pmc_ctx* ctx, unsigned step, float r_bond, int min_nb, int table) {
+    enum { NB = 64 };
+    uint64_t h_size[NB], h_deg[128];
+    pmc_cluster_obs co;
+    int rc;
+    if ((rc = pmc_clusters(ctx, r_bond, min_nb, NB, h_size, h_deg, NULL, &co))) die("pmc_clusters", rc);
+    if (!table) {
+        printf("clusters %u count %lld largest %lld mean %.9g liquid %.9g (N %lld, core %lld, bonds %lld, "
+               "core bonds %lld, largest label %lld, sum s^2 %lld)\n", step, (long long)co.clusters,
+               (long long)co.largest, co.core ? (double)co.sum_s2 / (double)co.core : 0.0,
+               co.particles ? (double)co.core / (double)co.particles : 0.0, (long long)co.particles,
+               (long long)co.core, (long long)co.bonds, (long long)co.core_bonds, (long long)co.largest_label,
+               (long long)co.sum_s2);
+        return;
+    }
+    printf("# cluster sizes (r_bond %.9g, min_neighbours %d): size, clusters; the last bin holds sizes >= %d\n",
+           (double)r_bond, min_nb, (int)NB);
+    for (int b = 0; b < NB; ++b)
+        if (h_size[b]) printf("cluster_size %d %llu\n", b + 1, (unsigned long long)h_size[b]);
+}
+
 int main(int argc, char** argv) {
     pmc_params p;
     memset(&p, 0, sizeof(p));
@@ -104,7 +132,8 @@ int main(int argc, char** argv) {
     long long atoms = 64;
     int passes = 1000, every = 1, graph = 0, pairobs = 0, widom = 0, sk = 0, gc_moves = 1, gc_every = 1;
     int prof_axis = -1, prof_bins = 0, ik_axis = -1, ik_bins = 0;
-    float gcmc = 0.0f;
+    float gcmc = 0.0f, cl_rb = 0.0f;
+    int cl_minnb = 0;
     const char *dump = NULL, *save = NULL, *restart = NULL;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -146,6 +175,16 @@ int main(int argc, char** argv) {
             }
             ++i;
         }
+        else if (!strcmp(a, "--clusters")) {
+            const char* colon = strchr(v, ':');
+            cl_rb = (float)atof(v);
+            cl_minnb = colon ? atoi(colon + 1) : 0;
+            if (!(cl_rb > 0.0f) || cl_minnb < 0 || cl_minnb > 127) {
+                fprintf(stderr, "--clusters RB[:MINNB]: RB > 0, MINNB 0..127\n");
+                return 2;
+            }
+            ++i;
+        }
         else if (!strcmp(a, "--gcmc")) { gcmc = (float)atof(v); ++i; }
         else if (!strcmp(a, "--gc-moves")) { gc_moves = atoi(v); ++i; }
         else if (!strcmp(a, "--gc-every")) { gc_every = atoi(v); ++i; }
@@ -170,6 +209,7 @@ int main(int argc, char** argv) {
     rc = pmc_energy(ctx, &e);
     if (rc) die("pmc_energy", rc);
     printf("0: %f\n", e);
+    if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)first, cl_rb, cl_minnb, 0);
     pmc_stats total;
     memset(&total, 0, sizeof(total));
     double seconds = 0.0;
@@ -213,6 +253,7 @@ int main(int argc, char** argv) {
             total.de_fixed += r.stats.de_fixed;
         }
         if (gcmc == 0.0f) printf("%u: %f\n", (unsigned)(s + (uint32_t)k), e);
+        if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)(s + (uint32_t)k), cl_rb, cl_minnb, 0);
         if (dump && (rc = pmc_dump_frame(ctx, dump, 1, (int64_t)(s + (uint32_t)k)))) die("pmc_dump_frame", rc);
     }
     if (save && (rc = pmc_save_snapshot(ctx, save, first + (uint32_t)passes))) die("pmc_save_snapshot", rc);
@@ -221,6 +262,7 @@ int main(int argc, char** argv) {
            (long long)total.trials, (long long)total.evaluated);
     if (seconds > 0)
         printf("# device time %.6f s, %.3e trial-moves/s\n", seconds, (double)total.trials / seconds);
+    if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)(first + (uint32_t)passes), cl_rb, cl_minnb, 1);
     if (pairobs) {
         const double pi = 3.14159265358979323846;
         uint64_t* hist = calloc(pairobs > 0 ? (size_t)pairobs : 1, sizeof(uint64_t));

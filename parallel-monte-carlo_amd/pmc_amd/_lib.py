@@ -63,6 +63,13 @@ class ProfileObs(C.Structure):
     _fields_ = [("virial_fixed", C.c_int64), ("pairs", C.c_int64), ("particles", C.c_int64)]
 
 
+class ClusterObs(C.Structure):
+    """``pmc_cluster_obs``."""
+
+    _fields_ = [(k, C.c_int64) for k in ("particles", "core", "bonds", "core_bonds", "clusters", "largest",
+                                         "largest_label", "sum_s2")]
+
+
 class GcStats(C.Structure):
     """``pmc_gc_stats``."""
 
@@ -88,6 +95,7 @@ PMC_LAYOUT_REFERENCE, PMC_LAYOUT_PACKED = 0, 1
 PMC_PROBE_INSERT, PMC_PROBE_REAL = 0, 1     # include/pmc_probe.h
 PMC_SK_MAX_K, PMC_SK_MAX_H = 4096, 1024     # include/pmc_sk.h
 PMC_PROFILE_MAX_BINS, PMC_PROFILE_BINS_PER_CELL = 4096, 64     # include/pmc_profile.h
+PMC_CLUSTER_DEG_BINS, PMC_CLUSTER_MAX_BINS = 128, 4096     # include/pmc_cluster.h
 
 
 class PmcError(RuntimeError):
@@ -189,6 +197,7 @@ def lib():
         _sig(L, "pmc_density_modes", i32, _vp, _vp, i32, _vp, _vp, C.POINTER(SkObs))
         _sig(L, "pmc_profiles", i32, _vp, i32, i32, _vp, _vp, C.POINTER(ProfileObs))
         _sig(L, "pmc_profiles_ik", i32, _vp, i32, i32, _vp, _vp, C.POINTER(ProfileObs))
+        _sig(L, "pmc_clusters", i32, _vp, C.c_float, i32, i32, _vp, _vp, _vp, C.POINTER(ClusterObs))
         _sig(L, "pmc_exchange_phase", i32, _vp, i32, u32, C.c_float, i32)
         _sig(L, "pmc_exchange_sweep", i32, _vp, u32, C.c_float, i32)
         _sig(L, "pmc_gc_stats_read", i32, _vp, C.POINTER(GcStats), i32)

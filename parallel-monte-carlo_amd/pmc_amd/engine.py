@@ -21,8 +21,8 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT, PMC_PROBE_REAL, GcStats, PairObs, Params, ProbeObs,
-                   ProfileObs, Result, SkObs, Stats, check, lib)
+from ._lib import (PMC_CLUSTER_DEG_BINS, PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT, PMC_PROBE_REAL, ClusterObs, GcStats,
+                   PairObs, Params, ProbeObs, ProfileObs, Result, SkObs, Stats, check, lib)
 
 FIX_SCALE = 2.0 ** 32
 
@@ -442,6 +442,34 @@ class PmcContext:
         L = np.array([np.float32(self.cps_x) * w, np.float32(self.cps_y) * w, np.float32(self.cps_z) * w], np.float32)
         return {"count": count, "vir": ik, "virial_fixed": int(out.virial_fixed), "pairs": int(out.pairs),
                 "particles": int(out.particles), "axis": int(axis), "L": L, "contour": "ik"}
+
+    def clusters(self, r_bond: float = 1.5, min_neighbours: int = 0, nbins: int = 64, labels: bool = False) -> dict:
+        """Cluster analysis of a whole-box context (pmc_clusters, include/pmc_cluster.h): particles
+        within r_bond (<= w) of each other are bonded, a particle with at least min_neighbours bonds is
+        a core particle (0: every particle, plain Stillinger clusters; > 0: the ten Wolde-Frenkel
+        liquid-like criterion), and the clusters are the connected components of the core particles.
+        Returns size_hist (uint64, nbins: bin s - 1 counts the clusters of size s, the last bin the
+        sizes >= nbins), deg_hist (uint64, 128: bin d counts the particles with d bonds, the last bin
+        d >= 127), the integers particles, core, bonds, core_bonds (ordered pairs), clusters, largest,
+        largest_label and sum_s2, and r_bond, min_neighbours, nbins as used.  labels=True adds
+        "labels": int32 per slot (cell c, slot s at c * nmax + s, the order of copy_out's rows): the
+        smallest particle id of the slot's cluster, -1 for a particle that is not core and for an
+        empty slot; otherwise "labels" is None.  Every output is exact and independent of the launch
+        shape.  observables.cluster_size_distribution, largest_cluster, mean_cluster_size,
+        liquid_fraction and coordination_distribution convert; observables.add_clusters accumulates
+        samples.  Slab contexts are refused (a cluster can cross a slab face)."""
+        size_hist = np.zeros(max(int(nbins), 0), np.uint64)
+        deg_hist = np.zeros(PMC_CLUSTER_DEG_BINS, np.uint64)
+        lab = np.empty(self.cells * self.nmax, np.int32) if labels else None
+        out = ClusterObs()
+        check("pmc_clusters",
+              lib().pmc_clusters(self._h, r_bond, int(min_neighbours), int(nbins),
+                                 size_hist.ctypes.data if size_hist.size else None, deg_hist.ctypes.data,
+                                 lab.ctypes.data if labels else None, C.byref(out)))
+        res = {key: int(getattr(out, key)) for key, _ in ClusterObs._fields_}
+        res.update(size_hist=size_hist, deg_hist=deg_hist, labels=lab, r_bond=float(np.float32(r_bond)),
+                   min_neighbours=int(min_neighbours), nbins=int(nbins))
+        return res
 
     def stats(self, reset: bool = False) -> dict:
         s = Stats()

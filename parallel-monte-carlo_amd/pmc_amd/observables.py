@@ -5,7 +5,8 @@ chemical potential and energy distributions from those of ``PmcContext.probe_ene
 modes of ``PmcContext.density_modes`` (pmc_density_modes, include/pmc_sk.h), and the density and
 pressure-tensor profiles and the surface tension from the axis profiles of ``PmcContext.profiles``
 (pmc_profiles, include/pmc_profile.h) and ``PmcContext.profiles_ik`` (pmc_profiles_ik,
-include/pmc_profile_ik.h).
+include/pmc_profile_ik.h), and the cluster-size and coordination statistics from the integers of
+``PmcContext.clusters`` (pmc_clusters, include/pmc_cluster.h).
 
 Pure numpy, no GPU: the sums of several slab contexts are added first (they are exact integers),
 then converted here.  Units are the library's reduced Lennard-Jones units (epsilon = sigma_LJ = 1).
@@ -298,3 +299,64 @@ def shell_average(k, s, dk: float) -> tuple:
     with np.errstate(invalid="ignore", divide="ignore"):
         mean = np.where(counts > 0, sums / counts, np.nan)
     return (np.arange(nb) + 0.5) * dk, mean, counts
+
+
+# ---- cluster analysis (PmcContext.clusters) ----------------------------------------------------------
+_CLUSTER_SUMS = ("particles", "core", "bonds", "core_bonds", "clusters", "sum_s2")
+
+
+def add_clusters(a: dict, b: dict) -> dict:
+    """Accumulate two cluster results (samples of one run): the histograms and the counts add, largest
+    keeps the maximum over the samples (with that sample's largest_label), "samples" counts them, and
+    "largest_sum" adds the samples' largest sizes (largest_cluster's mean).  Labels are per sample and
+    are dropped.  Refuses results taken with a different r_bond, min_neighbours or nbins."""
+    for k in ("r_bond", "min_neighbours", "nbins"):
+        if a[k] != b[k]:
+            raise ValueError(f"add_clusters: results taken with different {k}")
+    out = dict(a)
+    out["size_hist"] = np.asarray(a["size_hist"], np.uint64) + np.asarray(b["size_hist"], np.uint64)
+    out["deg_hist"] = np.asarray(a["deg_hist"], np.uint64) + np.asarray(b["deg_hist"], np.uint64)
+    for k in _CLUSTER_SUMS:
+        out[k] = int(a[k]) + int(b[k])
+    out["samples"] = int(a.get("samples", 1)) + int(b.get("samples", 1))
+    out["largest_sum"] = int(a.get("largest_sum", a["largest"])) + int(b.get("largest_sum", b["largest"]))
+    top = a if int(a["largest"]) >= int(b["largest"]) else b
+    out["largest"], out["largest_label"] = int(top["largest"]), int(top["largest_label"])
+    out["labels"] = None
+    return out
+
+
+def cluster_size_distribution(res: dict) -> tuple:
+    """(sizes, clusters per sample, fraction of the core particles) per bin: sizes 1..nbins, the mean
+    number of clusters of each size per sample, and the share of the core particles that sit in
+    clusters of that size.  The last bin collects the sizes >= nbins: its particle share is what the
+    other bins leave of `core`."""
+    h = np.asarray(res["size_hist"], np.float64)
+    sizes = np.arange(1, len(h) + 1)
+    core = float(res["core"])
+    inside = sizes[:-1] * h[:-1]
+    share = np.append(inside, core - inside.sum()) / core if core > 0 else np.zeros(len(h))
+    return sizes, h / float(res.get("samples", 1)), share
+
+
+def largest_cluster(res: dict) -> float:
+    """Size of the largest cluster: of one sample, or the mean over accumulated samples."""
+    return float(res.get("largest_sum", res["largest"])) / float(res.get("samples", 1))
+
+
+def mean_cluster_size(res: dict) -> float:
+    """The weight-average cluster size sum s^2 / sum s over the clusters (sum s = core particles)."""
+    return float(res["sum_s2"]) / float(res["core"]) if int(res["core"]) > 0 else 0.0
+
+
+def liquid_fraction(res: dict) -> float:
+    """Core particles / particles: with min_neighbours > 0 the liquid-like fraction."""
+    return float(res["core"]) / float(res["particles"]) if int(res["particles"]) > 0 else 0.0
+
+
+def coordination_distribution(res: dict) -> tuple:
+    """(degrees 0..127, probability of each, mean degree): the coordination-number distribution of the
+    particles (the last bin collects degrees >= 127) and the exact mean bonds / particles."""
+    h = np.asarray(res["deg_hist"], np.float64)
+    n = float(res["particles"])
+    return np.arange(len(h)), (h / n if n > 0 else h), (float(res["bonds"]) / n if n > 0 else 0.0)
