@@ -462,6 +462,41 @@ typedef struct pmc_cluster_obs {
 } pmc_cluster_obs;
 int pmc_clusters(pmc_ctx* ctx, float r_bond, int min_neighbours, int nbins, uint64_t* h_size, uint64_t* h_deg,
                  int32_t* h_label, pmc_cluster_obs* out);
+/* Bond-orientational order of the owned cells' particles, defined bit for bit in pmc_boo.h: the
+ * Steinhardt order parameter q_l (l = 4 or 6) of every particle from integer spherical-harmonic sums
+ * Q_m(i) over its bonds (partners with r <= r_bond, pmc_cluster.h's walk), the q.q connection test
+ * D(i, j) * 256 > c8 * N(i) * N(j) on every bond (c8 / 256 is the threshold on the normalised
+ * product: 128 = 0.5, 179 = 0.7), the solid particles (at least min_conn connections; 0: every
+ * particle) and the clusters of solid particles under "bonded in either direction", labelled as
+ * pmc_clusters labels them.  The reference has no such observable.  All pointers are HOST pointers.
+ * h_q[nq]: bin min(nq - 1, nq * N / (deg * K_l)) counts the particles with that q_l (deg = 0 counts in
+ * out->isolated instead).  h_conn[128]: bin d counts the particles with d connections, the last bin
+ * d >= 127.  h_size[nbins]: as in pmc_clusters.  h_record (may be NULL): storage_cells * nmax records
+ * of 16 int32 in slot order: Q_0..Q_12 (the unused ones 0), N, deg, nconn; zeros in empty slots.
+ * h_label (may be NULL): as in pmc_clusters, -1 for a particle that is not solid.
+ * PMC_ERR_ARG (outputs untouched) for a null h_q, h_conn, h_size or out, l not 4 or 6, r_bond not
+ * finite, <= 0 or > w, c8 outside 0..256, min_conn outside 0..127, nq or nbins outside 1..4096,
+ * storage_cells * nmax >= 2^31, and for any slab context (halo != 0): the connection test needs the
+ * halo partners' Q_m, which no rank holds.  Runs on the context stream and synchronises; state,
+ * statistics, exchange counters, error flags and the energy are left unchanged.  Device scratch (64
+ * bytes per slot, plus pmc_clusters' 10 bytes per slot, which the two calls share) is allocated on the
+ * first call and freed by pmc_destroy; a failed allocation returns PMC_ERR_HIP and leaves the context
+ * usable. */
+typedef struct pmc_boo_obs {
+    int64_t particles;      /* particles in owned cells */
+    int64_t bonds;          /* ordered pairs with r2 <= rb2 (the sum of the degrees) */
+    int64_t isolated;       /* particles with deg = 0 (not in h_q) */
+    int64_t conn_bonds;     /* ordered pairs with conn(i, j) (the sum of nconn) */
+    int64_t solid;          /* solid particles: nconn >= min_conn */
+    int64_t solid_bonds;    /* ordered pairs with r2 <= rb2 and both ends solid */
+    int64_t clusters;       /* clusters (components of the solid particles) */
+    int64_t largest;        /* size of the largest cluster (0 without clusters) */
+    int64_t largest_label;  /* the smallest label among the clusters of that size (-1 without clusters) */
+    int64_t sum_s2;         /* sum over clusters of size^2 */
+    int64_t qsum[13];       /* sum over particles of Q_m: Q_l = sqrt(4pi/(2l+1) sum_m qsum_m^2) / (bonds 2^14) */
+} pmc_boo_obs;
+int pmc_bond_order(pmc_ctx* ctx, int l, float r_bond, int c8, int min_conn, int nq, int nbins, uint64_t* h_q,
+                   uint64_t* h_conn, uint64_t* h_size, int32_t* h_record, int32_t* h_label, pmc_boo_obs* out);
 /* ---- grand-canonical exchange moves (mu V T) ------------------------------------------------
  * Insertions and deletions as a further kind of colour phase, defined bit for bit in pmc_gc.h: every
  * owned cell of the colour runs k_per_cell (1..64) attempts in order on its own particle list, each

@@ -14,6 +14,7 @@
 #include "pmc_ctx.h"
 #include "../../include/pmc_pairobs.h"
 #include "../../include/pmc_cluster.h"
+#include "../../include/pmc_boo.h"
 #include "../../include/pmc_probe.h"
 #include "../../include/pmc_gc.h"
 #include "../../include/pmc_sk.h"
@@ -24,6 +25,9 @@ using namespace pmc_sched;
 
 static_assert(kPairObsMaxBins == PMC_PAIROBS_MAX_BINS, "pair observables: bin cap");
 static_assert(kClusterMaxBins == PMC_CLUSTER_MAX_BINS && kClusterDegBins == PMC_CLUSTER_DEG_BINS, "cluster analysis: bin caps");
+static_assert(kBooMaxBins == PMC_BOO_MAX_BINS && kBooConnBins == PMC_BOO_CONN_BINS && kBooRecord == PMC_BOO_RECORD &&
+                  kBooQsum + PMC_BOO_TERMS <= kBooHead && kBooOwn >= PMC_BOO_TERMS + 1,
+              "bond-orientational order: bin caps and record size");
 static_assert(kProbeMaxBins == PMC_PROBE_MAX_BINS, "test-particle energies: bin cap");
 static_assert(kSkMaxK == PMC_SK_MAX_K, "density modes: vector cap");
 static_assert(kGcCounters == PMC_GC_COUNTERS && sizeof(pmc_gc_stats) == 8 * PMC_GC_COUNTERS, "exchange moves: counters");
@@ -314,7 +318,8 @@ void pmc_destroy(pmc_ctx* c) {
     if (c->sk_acc) (void)hipFree(c->sk_acc);
     if (c->prof_acc) (void)hipFree(c->prof_acc);
     if (c->gc_acc) (void)hipFree(c->gc_acc);
-    for (void* m : {(void*)c->cl_parent, (void*)c->cl_size, (void*)c->cl_deg, (void*)c->cl_acc})
+    for (void* m : {(void*)c->cl_parent, (void*)c->cl_size, (void*)c->cl_deg, (void*)c->cl_acc, (void*)c->boo_rec,
+                    (void*)c->boo_acc})
         if (m) (void)hipFree(m);
     if (c->flags) (void)hipFree(c->flags);
     if (c->ovf) (void)hipFree(c->ovf);
@@ -709,6 +714,27 @@ int pmc_pair_observables(pmc_ctx* c, float r_max, int nbins, uint64_t* h_hist, p
     return PMC_OK;
 }
 
+// pmc_clusters' device scratch (shared with pmc_bond_order): all four buffers or none, so a failed
+// allocation leaves the context as it was
+static int cluster_scratch(pmc_ctx* c, size_t slots, const char* what) {
+    if (c->cl_acc) return PMC_OK;
+    hipError_t e = hipMalloc(&c->cl_parent, sizeof(int) * slots);
+    if (e == hipSuccess) e = hipMalloc(&c->cl_size, sizeof(unsigned) * slots);
+    if (e == hipSuccess) e = hipMalloc(&c->cl_deg, sizeof(uint16_t) * slots);
+    if (e == hipSuccess) e = hipMalloc(&c->cl_acc, sizeof(unsigned long long) * cluster_acc_words(kClusterMaxBins));
+    if (e != hipSuccess) {
+        for (void* m : {(void*)c->cl_parent, (void*)c->cl_size, (void*)c->cl_deg, (void*)c->cl_acc})
+            if (m) (void)hipFree(m);
+        c->cl_parent = nullptr;
+        c->cl_size = nullptr;
+        c->cl_deg = nullptr;
+        c->cl_acc = nullptr;
+        (void)hipGetLastError();   // the context stays usable
+        return hip_fail(e, what);
+    }
+    return PMC_OK;
+}
+
 int pmc_clusters(pmc_ctx* c, float r_bond, int min_neighbours, int nbins, uint64_t* h_size, uint64_t* h_deg,
                  int32_t* h_label, pmc_cluster_obs* out) {
     if (!c || !h_size || !h_deg || !out) return fail(PMC_ERR_ARG, "bad argument");
@@ -724,23 +750,7 @@ int pmc_clusters(pmc_ctx* c, float r_bond, int min_neighbours, int nbins, uint64
     if (slots64 >= ((int64_t)1 << 31)) return fail(PMC_ERR_ARG, "pmc_clusters: storage_cells * nmax must be below 2^31");
     const size_t slots = (size_t)slots64;
     if (int rj = slab_join(c)) return rj;
-    if (!c->cl_acc) {
-        // all four or none: a failed allocation leaves the context as it was
-        hipError_t e = hipMalloc(&c->cl_parent, sizeof(int) * slots);
-        if (e == hipSuccess) e = hipMalloc(&c->cl_size, sizeof(unsigned) * slots);
-        if (e == hipSuccess) e = hipMalloc(&c->cl_deg, sizeof(uint16_t) * slots);
-        if (e == hipSuccess) e = hipMalloc(&c->cl_acc, sizeof(unsigned long long) * cluster_acc_words(kClusterMaxBins));
-        if (e != hipSuccess) {
-            for (void* m : {(void*)c->cl_parent, (void*)c->cl_size, (void*)c->cl_deg, (void*)c->cl_acc})
-                if (m) (void)hipFree(m);
-            c->cl_parent = nullptr;
-            c->cl_size = nullptr;
-            c->cl_deg = nullptr;
-            c->cl_acc = nullptr;
-            (void)hipGetLastError();   // the context stays usable
-            return hip_fail(e, "pmc_clusters: scratch allocation");
-        }
-    }
+    if (int ra = cluster_scratch(c, slots, "pmc_clusters: scratch allocation")) return ra;
     const size_t words = cluster_acc_words(nbins);
     PMC_HIP(hipMemsetAsync(c->cl_parent, 0xFF, sizeof(int) * slots, c->stream));
     PMC_HIP(hipMemsetAsync(c->cl_size, 0, sizeof(unsigned) * slots, c->stream));
@@ -766,6 +776,81 @@ int pmc_clusters(pmc_ctx* c, float r_bond, int min_neighbours, int nbins, uint64
     out->largest = (int64_t)(tail[2] >> 32);
     out->largest_label = tail[0] ? (int64_t)(0x7FFFFFFFu - (uint32_t)(tail[2] & 0xFFFFFFFFull)) : -1;
     for (int b = 0; b < PMC_CLUSTER_DEG_BINS; ++b) h_deg[b] = (uint64_t)s[(size_t)kClusterHead + (size_t)b];
+    for (int b = 0; b < nbins; ++b) h_size[b] = (uint64_t)tail[(size_t)kClusterTail + (size_t)b];
+    return PMC_OK;
+}
+
+int pmc_bond_order(pmc_ctx* c, int l, float r_bond, int c8, int min_conn, int nq, int nbins, uint64_t* h_q,
+                   uint64_t* h_conn, uint64_t* h_size, int32_t* h_record, int32_t* h_label, pmc_boo_obs* out) {
+    if (!c || !h_q || !h_conn || !h_size || !out) return fail(PMC_ERR_ARG, "bad argument");
+    if (c->P.halo != 0)
+        return fail(PMC_ERR_ARG, "pmc_bond_order: whole-box contexts only (halo == 0): the connection test needs the "
+                                 "harmonic sums Q_m of the halo partners, which no rank holds");
+    if (l != 4 && l != 6) return fail(PMC_ERR_ARG, "pmc_bond_order: l must be 4 or 6");
+    if (!std::isfinite(r_bond) || !(r_bond > 0.0f) || r_bond > c->P.w)
+        return fail(PMC_ERR_ARG, "pmc_bond_order: r_bond must be finite, > 0 and <= w");
+    if (c8 < 0 || c8 > PMC_BOO_C8_ONE) return fail(PMC_ERR_ARG, "pmc_bond_order: c8 must be in 0..256");
+    if (min_conn < 0 || min_conn > PMC_BOO_MAX_MIN_CONN) return fail(PMC_ERR_ARG, "pmc_bond_order: min_conn must be in 0..127");
+    if (nq < 1 || nq > PMC_BOO_MAX_BINS || nbins < 1 || nbins > PMC_BOO_MAX_BINS)
+        return fail(PMC_ERR_ARG, "pmc_bond_order: nq and nbins must be in 1..4096");
+    const int64_t slots64 = c->cells * (int64_t)c->P.nmax;
+    if (slots64 >= ((int64_t)1 << 31)) return fail(PMC_ERR_ARG, "pmc_bond_order: storage_cells * nmax must be below 2^31");
+    const size_t slots = (size_t)slots64;
+    if (int rj = slab_join(c)) return rj;
+    if (int ra = cluster_scratch(c, slots, "pmc_bond_order: scratch allocation")) return ra;
+    if (!c->boo_acc) {
+        // both or none
+        hipError_t e = hipMalloc(&c->boo_rec, sizeof(int32_t) * kBooRecord * slots);
+        if (e == hipSuccess) e = hipMalloc(&c->boo_acc, sizeof(unsigned long long) * boo_acc_words(kBooMaxBins));
+        if (e != hipSuccess) {
+            if (c->boo_rec) (void)hipFree(c->boo_rec);
+            c->boo_rec = nullptr;
+            c->boo_acc = nullptr;
+            (void)hipGetLastError();   // the context stays usable
+            return hip_fail(e, "pmc_bond_order: scratch allocation");
+        }
+    }
+    const size_t cwords = cluster_acc_words(nbins), bwords = boo_acc_words(nq);
+    PMC_HIP(hipMemsetAsync(c->cl_parent, 0xFF, sizeof(int) * slots, c->stream));
+    PMC_HIP(hipMemsetAsync(c->cl_size, 0, sizeof(unsigned) * slots, c->stream));
+    PMC_HIP(hipMemsetAsync(c->cl_acc, 0, sizeof(unsigned long long) * cwords, c->stream));
+    PMC_HIP(hipMemsetAsync(c->boo_acc, 0, sizeof(unsigned long long) * bwords, c->stream));
+    hipError_t e = launch_bond_order(c->G, c->disk[c->cur], c->n[c->cur], l, pmc_cutoff_r2(r_bond), c8, min_conn, nq, nbins,
+                                     c->boo_rec, c->cl_parent, c->cl_size, c->cl_deg, c->boo_acc, c->cl_acc, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "bond-order analysis launch");
+    std::vector<unsigned long long> hc(cwords), hb(bwords);
+    std::vector<uint16_t> nconn(h_record ? slots : 0);
+    PMC_HIP(hipMemcpyAsync(hc.data(), c->cl_acc, sizeof(unsigned long long) * cwords, hipMemcpyDeviceToHost, c->stream));
+    PMC_HIP(hipMemcpyAsync(hb.data(), c->boo_acc, sizeof(unsigned long long) * bwords, hipMemcpyDeviceToHost, c->stream));
+    if (h_label) PMC_HIP(hipMemcpyAsync(h_label, c->cl_parent, sizeof(int32_t) * slots, hipMemcpyDeviceToHost, c->stream));
+    if (h_record) {
+        PMC_HIP(hipMemcpyAsync(h_record, c->boo_rec, sizeof(int32_t) * kBooRecord * slots, hipMemcpyDeviceToHost, c->stream));
+        PMC_HIP(hipMemcpyAsync(nconn.data(), c->cl_deg, sizeof(uint16_t) * slots, hipMemcpyDeviceToHost, c->stream));
+    }
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    // the device record's last word is 0: the connection counts sit in their own array (the link walk's degrees)
+    if (h_record)
+        for (size_t i = 0; i < slots; ++i) h_record[i * kBooRecord + (kBooRecord - 1)] = (int32_t)nconn[i];
+    const size_t per = boo_acc_stride(nq);
+    std::vector<unsigned long long> s(per, 0ull);
+    for (int k = 0; k < kBooCopies; ++k)
+        for (size_t i = 0; i < per; ++i) s[i] += hb[(size_t)k * per + i];
+    unsigned long long solid_bonds = 0;
+    for (int k = 0; k < kClusterCopies; ++k) solid_bonds += hc[(size_t)k * (kClusterHead + kClusterDegBins) + 3];
+    const unsigned long long* tail = hc.data() + (size_t)kClusterCopies * (kClusterHead + kClusterDegBins);
+    out->bonds = (int64_t)s[0];
+    out->particles = (int64_t)s[1];
+    out->isolated = (int64_t)s[2];
+    out->conn_bonds = (int64_t)s[3];
+    out->solid = (int64_t)s[4];
+    out->solid_bonds = (int64_t)solid_bonds;
+    out->clusters = (int64_t)tail[0];
+    out->sum_s2 = (int64_t)tail[1];
+    out->largest = (int64_t)(tail[2] >> 32);
+    out->largest_label = tail[0] ? (int64_t)(0x7FFFFFFFu - (uint32_t)(tail[2] & 0xFFFFFFFFull)) : -1;
+    for (int m = 0; m < PMC_BOO_TERMS; ++m) out->qsum[m] = (int64_t)s[(size_t)kBooQsum + (size_t)m];
+    for (int b = 0; b < PMC_BOO_CONN_BINS; ++b) h_conn[b] = (uint64_t)s[(size_t)kBooHead + (size_t)b];
+    for (int b = 0; b < nq; ++b) h_q[b] = (uint64_t)s[(size_t)kBooHead + kBooConnBins + (size_t)b];
     for (int b = 0; b < nbins; ++b) h_size[b] = (uint64_t)tail[(size_t)kClusterTail + (size_t)b];
     return PMC_OK;
 }

@@ -37,6 +37,9 @@ struct pmc_ctx {
     unsigned* cl_size = nullptr;               // storage_cells * nmax: particles per root
     uint16_t* cl_deg = nullptr;                // storage_cells * nmax: degrees
     unsigned long long* cl_acc = nullptr;      // cluster_acc_words(kClusterMaxBins)
+    // bond-orientational order: shares cl_* above; its own scratch is allocated together on first use
+    int* boo_rec = nullptr;                    // storage_cells * nmax records of kBooRecord int32
+    unsigned long long* boo_acc = nullptr;     // boo_acc_words(kBooMaxBins)
     unsigned long long* gc_acc = nullptr;      // exchange moves: accumulator copies (allocated on first use; kept until reset)
     uint32_t* flags = nullptr;
     int* ovf = nullptr;                   // subsweep overflow queue (1 + cells per colour)

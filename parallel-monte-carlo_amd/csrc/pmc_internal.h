@@ -229,6 +229,29 @@ constexpr size_t cluster_acc_words(int nbins) {
 hipError_t launch_clusters(const DevGeom& g, const float* disk, const int16_t* n, float rb2, int min_neighbours,
                            int nbins, int* parent, unsigned* size, uint16_t* deg, unsigned long long* acc,
                            hipStream_t st);
+// bond-orientational order (k_boo_accum, k_boo_conn, then k_cluster_walk's link form, k_cluster_flatten
+// and k_cluster_count; pmc_boo.h) of a whole-box context with slots = cells * nmax < 2^31.  rec: one
+// record of kBooRecord int32 per slot (Q[13], N, deg, 0), every slot written by the call.  parent, size,
+// nconn and cl_acc are launch_clusters' parent, size, deg and acc, prepared in the same way: nconn
+// takes the connection counts (0 in empty slots), cl_acc's copies [3] the ordered bonds between solid
+// particles and its tail the cluster counts; after the call parent holds the labels.  boo_acc, zeroed
+// on st before the call: kBooCopies copies of boo_acc_stride(nq) counters the host sums: [0] ordered
+// bonds, [1] owned particles, [2] particles without a bond, [3] connected ordered bonds, [4] solid
+// particles, [kBooQsum + m] the sum of Q_m (two's complement), then from kBooHead the connection
+// histogram (kBooConnBins) and the q_l histogram (nq).
+constexpr int kBooCopies = 32;
+constexpr int kBooHead = 24;
+constexpr int kBooQsum = 8;
+constexpr int kBooConnBins = 128;      // PMC_BOO_CONN_BINS
+constexpr int kBooMaxBins = 4096;      // PMC_BOO_MAX_BINS
+constexpr int kBooRecord = 16;         // PMC_BOO_RECORD
+constexpr int kBooOwn = 15;            // LDS ints per own particle in k_boo_conn (Q[13], N; odd: no bank conflicts)
+static_assert((kBooCopies & (kBooCopies - 1)) == 0, "accumulator copies: a power of two");
+__host__ __device__ constexpr size_t boo_acc_stride(int nq) { return (size_t)kBooHead + kBooConnBins + (size_t)nq; }
+constexpr size_t boo_acc_words(int nq) { return (size_t)kBooCopies * boo_acc_stride(nq); }
+hipError_t launch_bond_order(const DevGeom& g, const float* disk, const int16_t* n, int l, float rb2, int c8,
+                             int min_conn, int nq, int nbins, int* rec, int* parent, unsigned* size, uint16_t* nconn,
+                             unsigned long long* boo_acc, unsigned long long* cl_acc, hipStream_t st);
 // the cells of one colour of one plane: mode 0 plane -> packed buffer, 1 packed -> plane,
 // 2 plane -> plane; (cps_x/2)*(cps_y/2)*3*nmax floats
 hipError_t launch_colour_rows(const DevGeom& g, const float* src, float* dst, int colour, int mode, hipStream_t st);

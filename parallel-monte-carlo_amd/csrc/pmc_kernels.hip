@@ -27,6 +27,7 @@
 #include "../../include/pmc_detmath.h"
 #include "../../include/pmc_pairobs.h"
 #include "../../include/pmc_cluster.h"
+#include "../../include/pmc_boo.h"
 #include "../../include/pmc_probe.h"
 #include "../../include/pmc_gc.h"
 #include "../../include/pmc_sk.h"
@@ -3091,6 +3092,335 @@ __global__ __launch_bounds__(256) void k_cluster_count(const int* __restrict__ p
 }
 
 // ------------------------------------------------------------------------------------------
+// bond-orientational order (include/pmc_boo.h): two further walks in k_cluster_walk's per-cell form
+// (the same stencil, staging, chunks, pmc_box_d2 filter, LDS capacity and fixed grid), then the
+// cluster analysis' own link, flatten and count launches on the connections.
+//
+// k_boo_accum<.., L>: lane j holds staged partner j, own particle i is broadcast; hits are sparse
+// (about 12 of 130 staged partners at r_bond 1.5), so the harmonics run on the hit lanes only, under
+// a wave-uniform skip of the blocks without a hit.  Each hit lane adds its 2l + 1 integer terms to
+// the LDS table [own slot][2l + 1] with LDS integer atomics: integer sums do not depend on the
+// order.  Lane i then holds own particle i: it reads its row, forms N by the integer square root,
+// writes the 64-byte record (Q, N, deg; the lanes between the count and nmax write zero records, so
+// the scratch needs no memset), bins q_l in the wave's LDS histogram and keeps qsum in registers.
+//
+// k_boo_conn: every staged particle carries its id beside its position; the own particles' Q and N
+// are copied from the record scratch (complete: the previous launch) into LDS.  On a hit the lane
+// gathers the partner's record by id (4 x 16 bytes), forms D in int64 against the own particle's Q,
+// read from LDS at a wave-uniform address, and tests the connection; lane i keeps nconn(i) by
+// ballot and popcount, as the degree walk keeps deg.  It writes nconn to the u16 array the link
+// walk reads as its degrees and parent[id] = id for the solid particles (the others keep the
+// memset's -1), and bins nconn.  No wave waits for another; there is no grid barrier.
+// ------------------------------------------------------------------------------------------
+template <int NSLOT, bool OFF32, int L>   // L = 4, 6: accumulate; L = 0: connections
+__device__ __forceinline__ void boo_walk(const DevGeom& g, const float* __restrict__ disk,
+                                         const int16_t* __restrict__ ncnt, unsigned long long* __restrict__ acc,
+                                         uint32_t total_cells, float rb2, int nq, int c8, int min_conn,
+                                         int* __restrict__ rec, int* __restrict__ parent,
+                                         uint16_t* __restrict__ nconn_out) {
+    extern __shared__ __attribute__((aligned(16))) float csm[];
+    constexpr bool CONN = L == 0;
+    constexpr int NT = CONN ? kBooOwn : 2 * L + 1;   // ints per own particle in the LDS table
+    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
+    constexpr int CPP = kWave / HS;    // cells per staging pass
+    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
+    using DA = DiskAddr<OFF32>;
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int cap = 27 * nm;
+    float* ex_ = csm;
+    float* ey_ = csm + cap;
+    float* ez_ = csm + 2 * cap;
+    int* et_ = (int*)(csm + 3 * cap);              // connections: id of a staged particle
+    int* inv_l = et_ + (CONN ? cap : 0);           // list entry -> stencil lane (32 ints)
+    int* tab = inv_l + 32;                         // [kWave][NT]: accumulate: Q of the own particles; connections: Q and N
+    unsigned* hist = (unsigned*)(tab + kWave * NT);   // accumulate: nq bins of q_l; connections: kBooConnBins of nconn
+    const int nhist = CONN ? kBooConnBins : nq;
+    const int p = lane % HS;
+    const int ee = lane / HS;
+    unsigned long long n_pairs = 0, n_part = 0, n_spec = 0;    // wave-uniform; n_spec: isolated / solid
+    long long qs[CONN ? 1 : NT];                               // accumulate: this lane's share of qsum
+#pragma unroll
+    for (int m = 0; m < (CONN ? 1 : NT); ++m) qs[m] = 0;
+    for (int b = lane; b < nhist; b += kWave) hist[b] = 0u;
+    if (lane < 32) inv_l[lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+
+    // rows of the cell in flight (k_cluster_walk's issue_rows): slots [0, HS) of its occupied stencil cells
+    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
+    int vt[NPMAX];
+    bool vact[NPMAX];
+    int ncells = 0;
+    auto issue_rows = [&](const PairObsStencil& st) {
+        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
+        ncells = __popcll(mo);
+        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int q = 0; q < NPMAX; ++q) {
+            const int e = q * CPP + ee;
+            const int src = inv_l[e < ncells ? e : 0];
+            const int c_cnt = __shfl(st.cnt, src);
+            const int c_idx = __shfl(st.kc, src);
+            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
+            vact[q] = e < ncells && p < c_cnt;
+            vx[q] = vy[q] = vz[q] = 0.0f;
+            vt[q] = -1;
+            if (vact[q]) {
+                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
+                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
+                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
+                vy[q] = vy[q] + isy;
+                vz[q] = vz[q] + isz;
+                vt[q] = c_idx * nm + p;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
+    };
+
+    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
+    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
+        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
+        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
+        issue_rows(cur);
+        PairObsStencil nxt = cur;
+        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
+        for (int c = 0; c < ncl; ++c) {
+            // ---- stage cell c (k_cluster_walk's staging): own particles first, then the filtered partners
+            float blo[3], bhi[3];
+            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
+            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
+            int S = 0;
+            auto put = [&](bool act, float ux, float uy, float uz, int ut) {
+                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+                if (act) {
+                    const int dst = S + mbcnt64(am);
+                    ex_[dst] = ux;
+                    ey_[dst] = uy;
+                    ez_[dst] = uz;
+                    if constexpr (CONN) et_[dst] = ut;
+                }
+                S += __popcll(am);
+            };
+            // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles
+            auto chunks = [&](unsigned long long mg, bool filter) {
+                if constexpr (NSLOT > HS) {
+                    for (int s0 = HS; s0 < nm; s0 += HS) {
+                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
+                        while (ov) {
+                            int ks = 0, nc = 0;
+                            for (; nc < CPP && ov; ++nc) {
+                                const int kb = (int)__builtin_ctzll(ov);
+                                ov &= ov - 1ull;
+                                ks = ee == nc ? kb : ks;
+                            }
+                            const int c_cnt = __shfl(cur.cnt, ks);
+                            const int c_idx = __shfl(cur.kc, ks);
+                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
+                            const int ps = s0 + p;
+                            const bool act = ee < nc && ps < c_cnt;
+                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+                            int ut = -1;
+                            if (act) {
+                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
+                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+                                ux = ux + isx;
+                                uy = uy + isy;
+                                uz = uz + isz;
+                                ut = c_idx * nm + ps;
+                            }
+                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz, ut);
+                        }
+                    }
+                }
+            };
+            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
+            const int id0 = __builtin_amdgcn_readfirstlane(cur.kc) * nm;  // id of the own cell's slot 0
+            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
+            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0], vt[0]);      // own slots [0, HS)
+            chunks(1ull, false);                                          // own slots [HS, n)
+#pragma unroll
+            for (int q = 0; q < NPMAX; ++q) {
+                const int e = q * CPP + ee;
+                if (q * CPP < ncells)
+                    put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q], vt[q]);
+            }
+            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
+            // ---- the own particles' table: zeroed (accumulate), or Q and N from the records (connections)
+            const bool own = lane < n_own;
+            if constexpr (CONN) {
+                if (own) {
+                    const int4* r4 = (const int4*)(rec + (size_t)(id0 + lane) * kBooRecord);
+                    const int4 a = r4[0], b = r4[1], cc = r4[2], d = r4[3];
+                    int* o = tab + lane * NT;
+                    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+                    o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+                    o[8] = cc.x; o[9] = cc.y; o[10] = cc.z; o[11] = cc.w;
+                    o[12] = d.x; o[13] = d.y;
+                }
+            } else {
+                for (int k = lane; k < n_own * NT; k += kWave) tab[k] = 0;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            // ---- the next cell's rows go out now and arrive while this cell's pairs run
+            if (c + 1 < ncl) {
+                cur = nxt;
+                issue_rows(cur);
+                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
+            }
+            n_part += (unsigned long long)n_own;
+            if (n_own == 0) {
+                if constexpr (!CONN) {
+                    if (lane < nm) {   // an empty cell: zero records
+                        int4* r4 = (int4*)(rec + (size_t)(id0 + lane) * kBooRecord);
+                        r4[0] = r4[1] = r4[2] = r4[3] = make_int4(0, 0, 0, 0);
+                    }
+                } else {
+                    if (lane < nm) nconn_out[id0 + lane] = (uint16_t)0;
+                }
+                continue;
+            }
+            // ---- ordered pairs (i, j): lane j holds staged partner j (blocks of 64), own particle
+            //      i (staged first, in slot order: lane i of block 0) broadcast by readlane; j == i skipped
+            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+            int ot = -1;
+            if constexpr (CONN) ot = et_[lane];
+            int mycnt = 0;                                                 // lane i: deg(i) / nconn(i)
+            auto block = [&](int jb, auto first_c) {
+                constexpr bool kFirst = decltype(first_c)::value;
+                const int j = jb + lane;
+                const bool vj = j < S;
+                const int jj = vj ? j : 0;
+                float xj = ox, yj = oy, zj = oz;
+                int tj = ot;
+                if constexpr (!kFirst) {
+                    xj = ex_[jj];
+                    yj = ey_[jj];
+                    zj = ez_[jj];
+                    if constexpr (CONN) tj = et_[jj];
+                }
+                const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
+                for (int i = 0; i < n_own; ++i) {
+                    const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+                    const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+                    const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+                    const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
+                    const float r2 = pmc_r2(dx, dy, dz);
+                    unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rb2) & vm;
+                    if constexpr (kFirst) im &= ~(1ull << i);
+                    if (im == 0ull) continue;   // wave-uniform
+                    const bool hit = (im >> lane) & 1ull;
+                    int k = __popcll(im);
+                    if constexpr (CONN) {
+                        bool cn = false;
+                        if (hit) {
+                            const int4* r4 = (const int4*)(rec + (size_t)tj * kBooRecord);
+                            const int4 a = r4[0], b = r4[1], cc = r4[2], d = r4[3];
+                            const int qj[PMC_BOO_TERMS] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, cc.x, cc.y, cc.z, cc.w, d.x};
+                            const int* qi = tab + i * NT;
+                            long long D = 0;
+#pragma unroll
+                            for (int m = 0; m < PMC_BOO_TERMS; ++m) D += (long long)qi[m] * (long long)qj[m];
+                            cn = pmc_boo_conn(D, (long long)qi[13], (long long)d.y, c8);
+                        }
+                        k = __popcll(__builtin_amdgcn_ballot_w64(cn));
+                    } else {
+                        if (hit) {
+                            int32_t t[NT];
+                            if constexpr (L == 4) pmc_boo_terms4(dx, dy, dz, r2, t);
+                            else pmc_boo_terms6(dx, dy, dz, r2, t);
+                            int* row = tab + i * NT;
+#pragma unroll
+                            for (int m = 0; m < NT; ++m)
+                                (void)__hip_atomic_fetch_add(row + m, t[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                    }
+                    n_pairs += (unsigned long long)k;
+                    mycnt += lane == i ? k : 0;
+                }
+            };
+            block(0, std::true_type{});
+            for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the table's atomics have landed
+            if constexpr (CONN) {
+                const bool solid = own && mycnt >= min_conn;
+                if (lane < nm) nconn_out[id0 + lane] = (uint16_t)(own ? mycnt : 0);   // at most 27 * 64 - 1
+                if (solid) parent[id0 + lane] = id0 + lane;
+                if (own)
+                    (void)__hip_atomic_fetch_add(&hist[pmc_boo_conn_bin(mycnt)], 1u, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+                n_spec += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(solid));
+            } else {
+                int32_t q[PMC_BOO_RECORD];
+#pragma unroll
+                for (int m = 0; m < PMC_BOO_RECORD; ++m) q[m] = 0;
+                if (own) {
+#pragma unroll
+                    for (int m = 0; m < NT; ++m) {
+                        q[m] = tab[lane * NT + m];
+                        qs[m] += (long long)q[m];
+                    }
+                    q[13] = (int32_t)pmc_boo_norm(q);
+                    q[14] = mycnt;
+                    if (mycnt > 0)
+                        (void)__hip_atomic_fetch_add(&hist[pmc_boo_q_bin((int64_t)q[13], mycnt, L, nq)], 1u,
+                                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                if (lane < nm) {
+                    int4* r4 = (int4*)(rec + (size_t)(id0 + lane) * kBooRecord);
+                    r4[0] = make_int4(q[0], q[1], q[2], q[3]);
+                    r4[1] = make_int4(q[4], q[5], q[6], q[7]);
+                    r4[2] = make_int4(q[8], q[9], q[10], q[11]);
+                    r4[3] = make_int4(q[12], q[13], q[14], 0);
+                }
+                n_spec += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(own && mycnt == 0));
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_ and tab
+        }
+    }
+    // ---- flush into this wave's accumulator copy (pmc_internal.h states the layout)
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kBooCopies - 1)) * boo_acc_stride(nq);
+    if constexpr (CONN) {
+        if (lane == 0 && n_pairs != 0) atomicAdd(&mine[3], n_pairs);
+        if (lane == 1 && n_spec != 0) atomicAdd(&mine[4], n_spec);
+    } else {
+        const unsigned long long head3 = lane == 0 ? n_pairs : (lane == 1 ? n_part : n_spec);
+        if (lane < 3 && head3 != 0) atomicAdd(&mine[lane], head3);
+#pragma unroll
+        for (int m = 0; m < NT; ++m) {
+            long long v = qs[m];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            if (lane == 0 && v != 0) atomicAdd(&mine[kBooQsum + m], (unsigned long long)v);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    unsigned long long* gh = mine + kBooHead + (CONN ? 0 : kBooConnBins);
+    for (int b = lane; b < nhist; b += kWave) {
+        const unsigned h = hist[b];
+        if (h) atomicAdd(&gh[b], (unsigned long long)h);
+    }
+}
+
+template <int NSLOT, bool OFF32, int L>
+__global__ __launch_bounds__(kWave) void k_boo_accum(DevGeom g, const float* __restrict__ disk,
+                                                     const int16_t* __restrict__ ncnt,
+                                                     unsigned long long* __restrict__ acc, uint32_t total_cells,
+                                                     float rb2, int nq, int* __restrict__ rec) {
+    static_assert(L == 4 || L == 6, "l is 4 or 6");
+    boo_walk<NSLOT, OFF32, L>(g, disk, ncnt, acc, total_cells, rb2, nq, 0, 0, rec, nullptr, nullptr);
+}
+
+template <int NSLOT, bool OFF32>
+__global__ __launch_bounds__(kWave) void k_boo_conn(DevGeom g, const float* __restrict__ disk,
+                                                    const int16_t* __restrict__ ncnt,
+                                                    unsigned long long* __restrict__ acc, uint32_t total_cells,
+                                                    float rb2, int nq, int c8, int min_conn, int* __restrict__ rec,
+                                                    int* __restrict__ parent, uint16_t* __restrict__ nconn) {
+    boo_walk<NSLOT, OFF32, 0>(g, disk, ncnt, acc, total_cells, rb2, nq, c8, min_conn, rec, parent, nconn);
+}
+
+// ------------------------------------------------------------------------------------------
 // test-particle energies (include/pmc_probe.h): per owned cell, kpc Widom insertions at Philox
 // positions (PMC_PROBE_INSERT) or the cell's own particles with their own slot skipped
 // (PMC_PROBE_REAL), each against the cell's 27-cell stencil.  k_pairobs' per-cell form: the same
@@ -5124,6 +5454,48 @@ hipError_t launch_clusters(const DevGeom& g, const float* disk, const int16_t* n
     hipLaunchKernelGGL(k_cluster_flatten, grid_s, block_s, 0, st, parent, size, (uint32_t)slots);
     hipLaunchKernelGGL(k_cluster_count, grid_s, block_s, sizeof(unsigned) * (size_t)nbins, st, parent, size,
                        (uint32_t)slots, acc + (size_t)kClusterCopies * (kClusterHead + kClusterDegBins), nbins);
+    return hipGetLastError();
+}
+
+// The bond-order analysis' launches (pmc_internal.h states the buffers): the two walks of pmc_boo.h on
+// launch_clusters' grid, then the cluster analysis' link walk, flatten and count, unchanged, with the
+// connection counts as the degrees and min_conn as min_neighbours.  LDS per wave at nmax 16 and l = 6:
+// 8.9 KiB + 4 nq bytes for the accumulation, 11.2 KiB for the connections.
+hipError_t launch_bond_order(const DevGeom& g, const float* disk, const int16_t* n, int l, float rb2, int c8,
+                             int min_conn, int nq, int nbins, int* rec, int* parent, unsigned* size, uint16_t* nconn,
+                             unsigned long long* boo_acc, unsigned long long* cl_acc, hipStream_t st) {
+    if (nbins < 1 || nbins > kClusterMaxBins || nq < 1 || nq > kBooMaxBins || g.halo != 0 || (l != 4 && l != 6) ||
+        min_conn < 0 || c8 < 0 || c8 > 256)
+        return hipErrorInvalidValue;
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells = storage cells
+    const int64_t slots = total * g.nmax;
+    if (slots >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
+    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
+    const size_t stage = 3 * 27 * (size_t)g.nmax + 32;
+    const size_t lds_acc = sizeof(float) * (stage + (size_t)kWave * (2 * l + 1) + (size_t)nq);
+    const size_t lds_conn = sizeof(float) * (stage + 27 * (size_t)g.nmax + (size_t)kWave * kBooOwn + kBooConnBins);
+    const size_t lds_link = sizeof(float) * (4 * 27 * (size_t)g.nmax + 32);
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
+    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
+        if (l == 4)
+            hipLaunchKernelGGL((k_boo_accum<NS, O, 4>), grid, block, lds_acc, st, g, disk, n, boo_acc, (uint32_t)total,
+                               rb2, nq, rec);
+        else
+            hipLaunchKernelGGL((k_boo_accum<NS, O, 6>), grid, block, lds_acc, st, g, disk, n, boo_acc, (uint32_t)total,
+                               rb2, nq, rec);
+        hipLaunchKernelGGL((k_boo_conn<NS, O>), grid, block, lds_conn, st, g, disk, n, boo_acc, (uint32_t)total, rb2, nq,
+                           c8, min_conn, rec, parent, nconn);
+        hipLaunchKernelGGL((k_cluster_walk<NS, O, true>), grid, block, lds_link, st, g, disk, n, cl_acc, (uint32_t)total,
+                           rb2, min_conn, parent, nconn);
+    });
+    const int64_t nb = (slots + 255) / 256;
+    const dim3 grid_s((unsigned)(nb < 4096 ? nb : 4096)), block_s(256);
+    hipLaunchKernelGGL(k_cluster_flatten, grid_s, block_s, 0, st, parent, size, (uint32_t)slots);
+    hipLaunchKernelGGL(k_cluster_count, grid_s, block_s, sizeof(unsigned) * (size_t)nbins, st, parent, size,
+                       (uint32_t)slots, cl_acc + (size_t)kClusterCopies * (kClusterHead + kClusterDegBins), nbins);
     return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
  *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS] [--widom K]
  *         [--sk HMAX] [--profile AXIS[:NBINS]] [--profile-ik AXIS[:NBINS]]
  *         [--gcmc Z [--gc-moves K] [--gc-every M]] [--clusters RB[:MINNB]]
+ *         [--boo L:RB[:THRESH[:MINCONN]]]
  *
  * --dump writes create_dump frames (kernel.cu:510-536; the reference's VISUALISATION path) of the
  * initial state and after every --every sweeps; --save writes a PMCSNAP1 snapshot at the end;
@@ -41,6 +42,13 @@
  * line with the sweep index, the number of clusters, the largest one's size, the weight-average size
  * sum s^2 / sum s and the core ("liquid-like") fraction, then the integers behind them; at the end the
  * final state's size table, one `cluster_size` line per occupied bin of 64 (the last: sizes >= 64).
+ *
+ * --boo L:RB[:THRESH[:MINCONN]] runs the bond-orientational order analysis (pmc_bond_order: l = 4 or 6,
+ * bond length RB <= w, a bond is connected above THRESH, default 0.7, applied as round(256 THRESH) / 256,
+ * a solid particle has at least MINCONN connected bonds, default 7) with every report: one `boo` line
+ * with the sweep index, the global order parameter Q_l, the mean local <q_l>, the number of solid
+ * particles, the number of solid clusters and the largest one's size, then the integers behind them;
+ * at the end the final state's q_l table, one `boo_q` line per occupied bin of 100.
  *
  * Prints "step: energy" lines like kernel.cu:643,695 (energy from the cell-list sum every
  * --every sweeps) and a final summary with acceptance ratio and trial-moves/s.  Compile-time
@@ -124,6 +132,34 @@ static void print_clusters(pmc_ctx* ctx, unsigned step, float r_bond, int min_nb
         if (h_size[b]) printf("cluster_size %d %llu\n", b + 1, (unsigned long long)h_size[b]);
 }
 
+/* --boo: the report line of the current state (table 0) or its q_l table (table 1) */
+static void print_boo(pmc_ctx* ctx, unsigned step, int l, float r_bond, int c8, int min_conn, int table) {
+    enum { NB = 64, NQ = 100 };
+    uint64_t h_q[NQ], h_conn[128], h_size[NB];
+    pmc_boo_obs bo;
+    int rc;
+    if ((rc = pmc_bond_order(ctx, l, r_bond, c8, min_conn, NQ, NB, h_q, h_conn, h_size, NULL, NULL, &bo)))
+        die("pmc_bond_order", rc);
+    if (!table) {
+        const double pi = 3.14159265358979323846;
+        double s2 = 0.0, qmean = 0.0;
+        uint64_t bonded = 0;
+        for (int m = 0; m < 13; ++m) s2 += (double)bo.qsum[m] * (double)bo.qsum[m];
+        for (int b = 0; b < NQ; ++b) { qmean += ((double)b + 0.5) / NQ * (double)h_q[b]; bonded += h_q[b]; }
+        printf("boo %u Q%d %.9g q%d %.9g solid %lld clusters %lld largest %lld (N %lld, bonds %lld, isolated %lld, "
+               "connected bonds %lld, solid bonds %lld, largest label %lld, sum s^2 %lld)\n", step, l,
+               bo.bonds ? sqrt(4.0 * pi / (2 * l + 1) * s2) / ((double)bo.bonds * 16384.0) : 0.0, l,
+               bonded ? qmean / (double)bonded : 0.0, (long long)bo.solid, (long long)bo.clusters, (long long)bo.largest,
+               (long long)bo.particles, (long long)bo.bonds, (long long)bo.isolated, (long long)bo.conn_bonds,
+               (long long)bo.solid_bonds, (long long)bo.largest_label, (long long)bo.sum_s2);
+        return;
+    }
+    printf("# local order q%d (r_bond %.9g, threshold %d/256, min_conn %d): bin centre, particles; the last bin "
+           "holds q >= %.2f\n", l, (double)r_bond, c8, min_conn, (double)(NQ - 1) / NQ);
+    for (int b = 0; b < NQ; ++b)
+        if (h_q[b]) printf("boo_q %.3f %llu\n", ((double)b + 0.5) / NQ, (unsigned long long)h_q[b]);
+}
+
 int main(int argc, char** argv) {
     pmc_params p;
     memset(&p, 0, sizeof(p));
@@ -133,7 +169,8 @@ int main(int argc, char** argv) {
     int passes = 1000, every = 1, graph = 0, pairobs = 0, widom = 0, sk = 0, gc_moves = 1, gc_every = 1;
     int prof_axis = -1, prof_bins = 0, ik_axis = -1, ik_bins = 0;
     float gcmc = 0.0f, cl_rb = 0.0f;
-    int cl_minnb = 0;
+    int cl_minnb = 0, boo_l = 0, boo_c8 = 179, boo_minconn = 7;
+    float boo_rb = 0.0f;
     const char *dump = NULL, *save = NULL, *restart = NULL;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -185,6 +222,21 @@ int main(int argc, char** argv) {
             }
             ++i;
         }
+        else if (!strcmp(a, "--boo")) {
+            const char* c1 = strchr(v, ':');
+            const char* c2 = c1 ? strchr(c1 + 1, ':') : NULL;
+            const char* c3 = c2 ? strchr(c2 + 1, ':') : NULL;
+            boo_l = atoi(v);
+            boo_rb = c1 ? (float)atof(c1 + 1) : 0.0f;
+            if (c2) boo_c8 = (int)floor(256.0 * atof(c2 + 1) + 0.5);
+            if (c3) boo_minconn = atoi(c3 + 1);
+            if ((boo_l != 4 && boo_l != 6) || !(boo_rb > 0.0f) || boo_c8 < 0 || boo_c8 > 256 || boo_minconn < 0 ||
+                boo_minconn > 127) {
+                fprintf(stderr, "--boo L:RB[:THRESH[:MINCONN]]: L 4 or 6, RB > 0, THRESH 0..1, MINCONN 0..127\n");
+                return 2;
+            }
+            ++i;
+        }
         else if (!strcmp(a, "--gcmc")) { gcmc = (float)atof(v); ++i; }
         else if (!strcmp(a, "--gc-moves")) { gc_moves = atoi(v); ++i; }
         else if (!strcmp(a, "--gc-every")) { gc_every = atoi(v); ++i; }
@@ -210,6 +262,7 @@ int main(int argc, char** argv) {
     if (rc) die("pmc_energy", rc);
     printf("0: %f\n", e);
     if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)first, cl_rb, cl_minnb, 0);
+    if (boo_l) print_boo(ctx, (unsigned)first, boo_l, boo_rb, boo_c8, boo_minconn, 0);
     pmc_stats total;
     memset(&total, 0, sizeof(total));
     double seconds = 0.0;
@@ -254,6 +307,7 @@ int main(int argc, char** argv) {
         }
         if (gcmc == 0.0f) printf("%u: %f\n", (unsigned)(s + (uint32_t)k), e);
         if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)(s + (uint32_t)k), cl_rb, cl_minnb, 0);
+        if (boo_l) print_boo(ctx, (unsigned)(s + (uint32_t)k), boo_l, boo_rb, boo_c8, boo_minconn, 0);
         if (dump && (rc = pmc_dump_frame(ctx, dump, 1, (int64_t)(s + (uint32_t)k)))) die("pmc_dump_frame", rc);
     }
     if (save && (rc = pmc_save_snapshot(ctx, save, first + (uint32_t)passes))) die("pmc_save_snapshot", rc);
@@ -263,6 +317,7 @@ int main(int argc, char** argv) {
     if (seconds > 0)
         printf("# device time %.6f s, %.3e trial-moves/s\n", seconds, (double)total.trials / seconds);
     if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)(first + (uint32_t)passes), cl_rb, cl_minnb, 1);
+    if (boo_l) print_boo(ctx, (unsigned)(first + (uint32_t)passes), boo_l, boo_rb, boo_c8, boo_minconn, 1);
     if (pairobs) {
         const double pi = 3.14159265358979323846;
         uint64_t* hist = calloc(pairobs > 0 ? (size_t)pairobs : 1, sizeof(uint64_t));

@@ -70,6 +70,13 @@ class ClusterObs(C.Structure):
                                          "largest_label", "sum_s2")]
 
 
+class BooObs(C.Structure):
+    """``pmc_boo_obs``."""
+
+    _fields_ = [(k, C.c_int64) for k in ("particles", "bonds", "isolated", "conn_bonds", "solid", "solid_bonds",
+                                         "clusters", "largest", "largest_label", "sum_s2")] + [("qsum", C.c_int64 * 13)]
+
+
 class GcStats(C.Structure):
     """``pmc_gc_stats``."""
 
@@ -96,6 +103,7 @@ PMC_PROBE_INSERT, PMC_PROBE_REAL = 0, 1     # include/pmc_probe.h
 PMC_SK_MAX_K, PMC_SK_MAX_H = 4096, 1024     # include/pmc_sk.h
 PMC_PROFILE_MAX_BINS, PMC_PROFILE_BINS_PER_CELL = 4096, 64     # include/pmc_profile.h
 PMC_CLUSTER_DEG_BINS, PMC_CLUSTER_MAX_BINS = 128, 4096     # include/pmc_cluster.h
+PMC_BOO_CONN_BINS, PMC_BOO_RECORD, PMC_BOO_TERMS = 128, 16, 13     # include/pmc_boo.h
 
 
 class PmcError(RuntimeError):
@@ -198,6 +206,8 @@ def lib():
         _sig(L, "pmc_profiles", i32, _vp, i32, i32, _vp, _vp, C.POINTER(ProfileObs))
         _sig(L, "pmc_profiles_ik", i32, _vp, i32, i32, _vp, _vp, C.POINTER(ProfileObs))
         _sig(L, "pmc_clusters", i32, _vp, C.c_float, i32, i32, _vp, _vp, _vp, C.POINTER(ClusterObs))
+        _sig(L, "pmc_bond_order", i32, _vp, i32, C.c_float, i32, i32, i32, i32, _vp, _vp, _vp, _vp, _vp,
+             C.POINTER(BooObs))
         _sig(L, "pmc_exchange_phase", i32, _vp, i32, u32, C.c_float, i32)
         _sig(L, "pmc_exchange_sweep", i32, _vp, u32, C.c_float, i32)
         _sig(L, "pmc_gc_stats_read", i32, _vp, C.POINTER(GcStats), i32)

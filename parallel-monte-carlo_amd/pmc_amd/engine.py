@@ -21,8 +21,9 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (PMC_CLUSTER_DEG_BINS, PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT, PMC_PROBE_REAL, ClusterObs, GcStats,
-                   PairObs, Params, ProbeObs, ProfileObs, Result, SkObs, Stats, check, lib)
+from ._lib import (PMC_BOO_CONN_BINS, PMC_BOO_RECORD, PMC_CLUSTER_DEG_BINS, PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT,
+                   PMC_PROBE_REAL, BooObs, ClusterObs, GcStats, PairObs, Params, ProbeObs, ProfileObs, Result, SkObs,
+                   Stats, check, lib)
 
 FIX_SCALE = 2.0 ** 32
 
@@ -469,6 +470,45 @@ class PmcContext:
         res = {key: int(getattr(out, key)) for key, _ in ClusterObs._fields_}
         res.update(size_hist=size_hist, deg_hist=deg_hist, labels=lab, r_bond=float(np.float32(r_bond)),
                    min_neighbours=int(min_neighbours), nbins=int(nbins))
+        return res
+
+    def bond_order(self, l: int = 6, r_bond: float = 1.5, threshold: float = 0.7, min_conn: int = 7, nq: int = 100,
+                   nbins: int = 64, records: bool = False, labels: bool = False) -> dict:
+        """Bond-orientational order of a whole-box context (pmc_bond_order, include/pmc_boo.h): the
+        Steinhardt order parameter q_l (l = 4 or 6) of every particle over its bonds (partners within
+        r_bond <= w), the connected bonds (normalised q(i).q(j) above `threshold`, applied exactly as
+        c8 / 256 with c8 = round(256 threshold)), the solid particles (at least min_conn connected
+        bonds; 0: every particle) and the clusters of solid particles.  Returns q_hist (uint64, nq
+        bins of q_l on [0, 1)), conn_hist (uint64, 128: particles by number of connected bonds),
+        size_hist (uint64, nbins, as clusters()), qsum (int64, 13: the sums of the integer harmonic
+        sums over the particles), the integers particles, bonds, isolated, conn_bonds, solid,
+        solid_bonds, clusters, largest, largest_label and sum_s2, core (= solid, so that
+        observables.cluster_size_distribution, largest_cluster and mean_cluster_size work on the
+        result), and l, r_bond, c8, threshold (the exact c8 / 256), min_conn, nq, nbins as used.
+        records=True adds "records": int32 (slots, 16) in slot order, Q_0..Q_12, N, deg, nconn, zeros in
+        empty slots (q_l = N / (deg K_l), K_4 = 13866, K_6 = 16664); labels=True adds "labels" as
+        clusters() does, -1 for a particle that is not solid.  Every output is exact and independent
+        of the launch shape.  observables.steinhardt_distribution, mean_local_order, global_order,
+        solid_fraction and connection_distribution convert; observables.add_bond_order accumulates
+        samples.  Slab contexts are refused (the connection test needs the halo partners' sums)."""
+        c8 = int(np.floor(256.0 * float(threshold) + 0.5))
+        slots = self.cells * self.nmax
+        q_hist = np.zeros(max(int(nq), 0), np.uint64)
+        conn_hist = np.zeros(PMC_BOO_CONN_BINS, np.uint64)
+        size_hist = np.zeros(max(int(nbins), 0), np.uint64)
+        rec = np.empty((slots, PMC_BOO_RECORD), np.int32) if records else None
+        lab = np.empty(slots, np.int32) if labels else None
+        out = BooObs()
+        check("pmc_bond_order",
+              lib().pmc_bond_order(self._h, int(l), r_bond, c8, int(min_conn), int(nq), int(nbins),
+                                   q_hist.ctypes.data if q_hist.size else None, conn_hist.ctypes.data,
+                                   size_hist.ctypes.data if size_hist.size else None,
+                                   rec.ctypes.data if records else None, lab.ctypes.data if labels else None,
+                                   C.byref(out)))
+        res = {key: int(getattr(out, key)) for key, _ in BooObs._fields_ if key != "qsum"}
+        res.update(qsum=np.array(list(out.qsum), np.int64), q_hist=q_hist, conn_hist=conn_hist, size_hist=size_hist,
+                   records=rec, labels=lab, l=int(l), r_bond=float(np.float32(r_bond)), c8=c8, threshold=c8 / 256.0,
+                   min_conn=int(min_conn), nq=int(nq), nbins=int(nbins), core=int(out.solid))
         return res
 
     def stats(self, reset: bool = False) -> dict:

@@ -6,7 +6,8 @@ modes of ``PmcContext.density_modes`` (pmc_density_modes, include/pmc_sk.h), and
 pressure-tensor profiles and the surface tension from the axis profiles of ``PmcContext.profiles``
 (pmc_profiles, include/pmc_profile.h) and ``PmcContext.profiles_ik`` (pmc_profiles_ik,
 include/pmc_profile_ik.h), and the cluster-size and coordination statistics from the integers of
-``PmcContext.clusters`` (pmc_clusters, include/pmc_cluster.h).
+``PmcContext.clusters`` (pmc_clusters, include/pmc_cluster.h), and the Steinhardt order-parameter
+statistics from those of ``PmcContext.bond_order`` (pmc_bond_order, include/pmc_boo.h).
 
 Pure numpy, no GPU: the sums of several slab contexts are added first (they are exact integers),
 then converted here.  Units are the library's reduced Lennard-Jones units (epsilon = sigma_LJ = 1).
@@ -360,3 +361,73 @@ def coordination_distribution(res: dict) -> tuple:
     h = np.asarray(res["deg_hist"], np.float64)
     n = float(res["particles"])
     return np.arange(len(h)), (h / n if n > 0 else h), (float(res["bonds"]) / n if n > 0 else 0.0)
+
+
+# ---- bond-orientational order (PmcContext.bond_order) ------------------------------------------------
+_BOO_SUMS = ("particles", "bonds", "isolated", "conn_bonds", "solid", "core", "solid_bonds", "clusters", "sum_s2")
+
+
+def global_order(res: dict) -> float:
+    """The global Steinhardt order parameter Q_l = sqrt(4 pi / (2l+1) sum_m qsum_m^2) / (bonds 2^14) of one
+    sample (the bond-weighted average of the harmonics over the whole box: near 0 in a liquid, the
+    crystal's q_l in a single crystal), or the mean over accumulated samples."""
+    if "global_order_sum" in res:
+        return float(res["global_order_sum"]) / float(res["samples"])
+    if int(res["bonds"]) == 0:
+        return 0.0
+    s = sum(int(q) * int(q) for q in np.asarray(res["qsum"]).tolist())     # exact: Python integers
+    return float(np.sqrt(4.0 * np.pi / (2 * int(res["l"]) + 1) * float(s)) / (float(res["bonds"]) * 16384.0))
+
+
+def add_bond_order(a: dict, b: dict) -> dict:
+    """Accumulate two bond-order results (samples of one run): the histograms and the counts add, largest
+    keeps the maximum over the samples (with that sample's largest_label), "samples" counts them,
+    "largest_sum" adds the samples' largest sizes and "global_order_sum" the samples' Q_l -- Q_l is not
+    linear in qsum, so the sum of qsum over samples would be meaningless and qsum is dropped, as are
+    the per-sample records and labels.  Refuses results taken with a different l, r_bond, c8, min_conn,
+    nq or nbins."""
+    for k in ("l", "r_bond", "c8", "min_conn", "nq", "nbins"):
+        if a[k] != b[k]:
+            raise ValueError(f"add_bond_order: results taken with different {k}")
+    out = dict(a)
+    for k in ("q_hist", "conn_hist", "size_hist"):
+        out[k] = np.asarray(a[k], np.uint64) + np.asarray(b[k], np.uint64)
+    for k in _BOO_SUMS:
+        out[k] = int(a[k]) + int(b[k])
+    out["samples"] = int(a.get("samples", 1)) + int(b.get("samples", 1))
+    out["largest_sum"] = int(a.get("largest_sum", a["largest"])) + int(b.get("largest_sum", b["largest"]))
+    out["global_order_sum"] = (global_order(a) * int(a.get("samples", 1)) + global_order(b) * int(b.get("samples", 1)))
+    top = a if int(a["largest"]) >= int(b["largest"]) else b
+    out["largest"], out["largest_label"] = int(top["largest"]), int(top["largest_label"])
+    out.pop("qsum", None)
+    out["records"] = out["labels"] = None
+    return out
+
+
+def steinhardt_distribution(res: dict) -> tuple:
+    """(bin centres, p(q_l)): the probability density of the local order parameter q_l(i) = N(i) /
+    (deg(i) K_l) over the particles that have a bond, nq bins on [0, 1) (the last bin also collects
+    q_l >= 1); p integrates to 1."""
+    h = np.asarray(res["q_hist"], np.float64)
+    nq = len(h)
+    total = h.sum()
+    return (np.arange(nq) + 0.5) / nq, (h / total * nq if total > 0 else h)
+
+
+def mean_local_order(res: dict) -> float:
+    """<q_l> over the particles that have a bond, from the histogram (bin centres: exact to 1 / (2 nq))."""
+    centres, p = steinhardt_distribution(res)
+    return float((centres * p).sum() / len(p))
+
+
+def solid_fraction(res: dict) -> float:
+    """Solid particles / particles."""
+    return float(res["solid"]) / float(res["particles"]) if int(res["particles"]) > 0 else 0.0
+
+
+def connection_distribution(res: dict) -> tuple:
+    """(connections 0..127, probability of each, mean number): the distribution of the number of
+    connected bonds per particle (the last bin collects >= 127) and the exact mean conn_bonds / particles."""
+    h = np.asarray(res["conn_hist"], np.float64)
+    n = float(res["particles"])
+    return np.arange(len(h)), (h / n if n > 0 else h), (float(res["conn_bonds"]) / n if n > 0 else 0.0)
