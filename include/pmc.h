@@ -542,6 +542,63 @@ int pmc_particle_count(pmc_ctx* ctx, int64_t* n);
  * gc->de_fixed) / 2^32 equals e_final up to the float rounding of the displacement moves. */
 int pmc_start_gc(pmc_ctx* ctx, uint32_t first_sweep, int mc_passes, int gc_every, float activity, int k_per_cell,
                  pmc_result* out, pmc_gc_stats* gc);
+/* ---- isobaric volume moves (N P T) ------------------------------------------------------------
+ * A random walk in the cell width w, defined bit for bit in pmc_npt.h.  w is the cell width and the
+ * cutoff and L = cps * w, so a volume move changes w and scales every coordinate; cell membership,
+ * counts and the checkerboard stay, and the new energy follows from the sums of r^-12 and r^-6 over
+ * the pairs inside the cutoff.  The reference samples fixed V only (start.cu:237-260).  Note the
+ * ensemble: the cutoff scales with the box (pmc_npt.h; tail corrections are the caller's). */
+typedef struct pmc_npt_sums {
+    int64_t s12_fixed;  /* sum over ordered pairs of fixed(r^-12), 2^-32 units */
+    int64_t s6_fixed;   /* sum over ordered pairs of fixed(r^-6), 2^-32 units */
+    int64_t pairs;      /* ordered pairs with r2 <= rc2 */
+    int64_t particles;  /* particles in owned cells */
+} pmc_npt_sums;
+/* The pair sums of the owned cells' particles (k_npt_sums): U(q) = 2 (S12 q^12 - S6 q^6) at the scale
+ * q = w / w'.  Additive over slab contexts like pmc_pair_observables, with its pending-z-exchange
+ * refusal.  Runs on the context stream and synchronises; state, statistics and error flags are left
+ * unchanged. */
+int pmc_volume_sums(pmc_ctx* ctx, pmc_npt_sums* out);
+/* The unconditional affine rescale (k_rescale) to the cell width w_new: every occupied coordinate
+ * times w_new / w, clamped into its cell's new assign interval; *clamped (may be NULL) receives the
+ * number of clamped coordinates.  Also the way to compress a lattice start to a target density.
+ * Afterwards pmc_get_params, the sweep plan's shift distance and snapshots use the new w; a recorded
+ * sweep graph is dropped.  Synchronises.  PMC_ERR_ARG, with nothing changed, for a slab context
+ * (halo != 0), a w_new that is not finite and > 0, and a ratio w_new / w outside [7/8, 8/7]. */
+int pmc_rescale(pmc_ctx* ctx, float w_new, int64_t* clamped);
+typedef struct pmc_npt_move {
+    int32_t accepted;      /* 1: the state was rescaled to w_new */
+    int32_t out_of_range;  /* 1: w_new outside [w_min, w_max] (rejected; du, dv, lhs are 0) */
+    float w_old;
+    float w_new;           /* the trial width */
+    float t;               /* the threshold T */
+    int32_t pad_;
+    double du;             /* U(w_new) - U(w_old) from the pair sums */
+    double dv;             /* V(w_new) - V(w_old) */
+    double lhs;            /* beta (dU + P dV) - (3 N + 2) ln(w_new / w_old): accepted iff lhs < T */
+    int64_t clamped;       /* coordinates the rescale clamped (0 when rejected) */
+} pmc_npt_move;
+/* One volume move (sweep, index): pair sums, the decision on the host and, if accepted, the rescale;
+ * synchronises.  *out may be NULL.  PMC_ERR_ARG, with nothing changed, for a slab context, a pressure
+ * that is not finite, and ranges outside 0 < w_min <= w <= w_max, 0 < dw_max <= w_min / 8. */
+int pmc_volume_move(pmc_ctx* ctx, uint32_t sweep, uint32_t index, float pressure, float dw_max, float w_min,
+                    float w_max, pmc_npt_move* out);
+/* Volume-move counters, host side in the context; like the exchange counters they are not part of
+ * PMCSNAP1 snapshots. */
+typedef struct pmc_npt_stats {
+    int64_t trials;
+    int64_t accepted;
+    int64_t out_of_range;
+    int64_t clamped;      /* coordinates clamped by the accepted moves' rescales */
+    double du_sum;        /* sum of the accepted moves' dU */
+} pmc_npt_stats;
+int pmc_npt_stats_read(pmc_ctx* ctx, pmc_npt_stats* out, int reset);
+/* pmc_start with volume moves (whole box only): for s = first_sweep .. first_sweep+mc_passes-1
+ * pmc_sweep(s), then pmc_volume_move(s, 0, ...) whenever (s + 1) % vol_every == 0 (vol_every >= 1).
+ * *npt (may be NULL) receives the run's volume-move counters; e_initial + out->stats.de_fixed / 2^32 +
+ * npt->du_sum equals e_final up to float rounding. */
+int pmc_start_npt(pmc_ctx* ctx, uint32_t first_sweep, int mc_passes, int vol_every, float pressure, float dw_max,
+                  float w_min, float w_max, pmc_result* out, pmc_npt_stats* npt);
 /* Read and optionally reset the accumulated subsweep statistics (synchronises). */
 int pmc_stats_read(pmc_ctx* ctx, pmc_stats* out, int reset);
 /* Device error flags (bit 0: shift overflow, bit 1: assign overflow, bit 2: assign range, bits 3-4:

@@ -17,6 +17,7 @@
 #include "../../include/pmc_boo.h"
 #include "../../include/pmc_probe.h"
 #include "../../include/pmc_gc.h"
+#include "../../include/pmc_npt.h"
 #include "../../include/pmc_sk.h"
 #include "../../include/pmc_profile.h"
 
@@ -318,6 +319,7 @@ void pmc_destroy(pmc_ctx* c) {
     if (c->sk_acc) (void)hipFree(c->sk_acc);
     if (c->prof_acc) (void)hipFree(c->prof_acc);
     if (c->gc_acc) (void)hipFree(c->gc_acc);
+    if (c->npt_acc) (void)hipFree(c->npt_acc);
     for (void* m : {(void*)c->cl_parent, (void*)c->cl_size, (void*)c->cl_deg, (void*)c->cl_acc, (void*)c->boo_rec,
                     (void*)c->boo_acc})
         if (m) (void)hipFree(m);
@@ -1248,6 +1250,167 @@ int pmc_start_gc(pmc_ctx* c, uint32_t first, int mc_passes, int gc_every, float 
     if ((rc = pmc_error_flags(c, &fl, 0))) return rc;
     if (out) *out = r;
     if (gc) *gc = g1;
+    if (fl & 1u) return fail(PMC_ERR_OVERFLOW, "shiftCells: cell occupancy exceeded nmax");
+    return PMC_OK;
+}
+
+// ---- isobaric volume moves (pmc_npt.h) ----------------------------------------------------------
+namespace {
+
+static int npt_scratch(pmc_ctx* c) {
+    if (!c->npt_acc) PMC_HIP(hipMalloc(&c->npt_acc, sizeof(unsigned long long) * (kNptCopies * kNptHead + 1)));
+    return PMC_OK;
+}
+
+static int npt_sums(pmc_ctx* c, const char* fn, pmc_npt_sums* out) {
+    // the kernel reads both halos, as the energy does (energy_fixed)
+    if (slab_pending_zdir(c))
+        return fail(PMC_ERR_ARG, std::string(fn) + ": a slab halo exchange is pending (call pmc_slab_finish first)");
+    if (int rj = slab_join(c)) return rj;
+    if (int rc = npt_scratch(c)) return rc;
+    PMC_HIP(hipMemsetAsync(c->npt_acc, 0, sizeof(unsigned long long) * kNptCopies * kNptHead, c->stream));
+    hipError_t e = launch_npt_sums(c->G, c->disk[c->cur], c->n[c->cur], c->npt_acc, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "volume sums launch");
+    unsigned long long h[kNptCopies * kNptHead];
+    PMC_HIP(hipMemcpyAsync(h, c->npt_acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    unsigned long long s[kNptHead] = {};
+    for (int k = 0; k < kNptCopies; ++k)
+        for (int i = 0; i < kNptHead; ++i) s[i] += h[k * kNptHead + i];
+    out->s12_fixed = (int64_t)s[0];
+    out->s6_fixed = (int64_t)s[1];
+    out->pairs = (int64_t)s[2];
+    out->particles = (int64_t)s[3];
+    return PMC_OK;
+}
+
+// the rescale itself (whole box, w_new validated by the caller): the kernel, then the geometry.  The
+// sweep plan's shift distance is computed from c->P.w at every enqueue_sweep, so it follows; a recorded
+// graph has the old geometry baked into its kernel arguments and is dropped.
+static int npt_rescale(pmc_ctx* c, float w_new, int64_t* clamped) {
+    if (int rc = npt_scratch(c)) return rc;
+    unsigned long long* cl = c->npt_acc + kNptCopies * kNptHead;
+    PMC_HIP(hipMemsetAsync(cl, 0, sizeof(unsigned long long), c->stream));
+    const float s = w_new / c->P.w;
+    hipError_t e = launch_rescale(c->G, c->disk[c->cur], c->n[c->cur], s, w_new, cl, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "rescale launch");
+    unsigned long long h = 0;
+    PMC_HIP(hipMemcpyAsync(&h, cl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    c->P.w = w_new;
+    c->G = make_geom(c->P);
+    drop_graph(c);
+    if (clamped) *clamped = (int64_t)h;
+    return PMC_OK;
+}
+
+static int npt_args(const pmc_ctx* c, const char* fn, float pressure, float dw_max, float w_min, float w_max) {
+    const std::string f(fn);
+    if (c->P.halo) return fail(PMC_ERR_ARG, f + ": volume moves need the whole box (halo must be 0)");
+    if (!std::isfinite(pressure)) return fail(PMC_ERR_ARG, f + ": the pressure must be finite");
+    if (!pmc_npt_range_ok(c->P.w, dw_max, w_min, w_max))
+        return fail(PMC_ERR_ARG, f + ": 0 < w_min <= w <= w_max and 0 < dw_max <= w_min / 8 are required");
+    return PMC_OK;
+}
+
+}  // namespace
+
+int pmc_volume_sums(pmc_ctx* c, pmc_npt_sums* out) {
+    if (!c || !out) return fail(PMC_ERR_ARG, "bad argument");
+    return npt_sums(c, "pmc_volume_sums", out);
+}
+
+int pmc_rescale(pmc_ctx* c, float w_new, int64_t* clamped) {
+    if (!c) return fail(PMC_ERR_ARG, "null ctx");
+    if (c->P.halo) return fail(PMC_ERR_ARG, "pmc_rescale: needs the whole box (halo must be 0)");
+    if (!std::isfinite(w_new) || !(w_new > 0.0f)) return fail(PMC_ERR_ARG, "pmc_rescale: w_new must be finite and > 0");
+    const double a = (double)w_new, b = (double)c->P.w;   // exact products
+    if (a * 8.0 < b * 7.0 || a * 7.0 > b * 8.0)
+        return fail(PMC_ERR_ARG, "pmc_rescale: w_new / w must be in [7/8, 8/7] (rescale in several steps)");
+    return npt_rescale(c, w_new, clamped);
+}
+
+int pmc_volume_move(pmc_ctx* c, uint32_t sweep, uint32_t index, float pressure, float dw_max, float w_min,
+                    float w_max, pmc_npt_move* out) {
+    if (!c) return fail(PMC_ERR_ARG, "null ctx");
+    if (int rc = npt_args(c, "pmc_volume_move", pressure, dw_max, w_min, w_max)) return rc;
+    pmc_npt_move m;
+    std::memset(&m, 0, sizeof(m));
+    m.w_old = c->P.w;
+    m.w_new = pmc_npt_propose(c->P.seed, sweep, index, c->P.w, dw_max, &m.t);
+    if (!(m.w_new >= w_min) || !(m.w_new <= w_max)) {
+        m.out_of_range = 1;
+    } else {
+        pmc_npt_sums s;
+        if (int rc = npt_sums(c, "pmc_volume_move", &s)) return rc;
+        const int64_t cells = (int64_t)c->P.cps_x * c->P.cps_y * c->P.cps_z;
+        m.lhs = pmc_npt_lhs(c->P.beta, pressure, s.s12_fixed, s.s6_fixed, s.particles, cells, m.w_old, m.w_new, &m.du,
+                            &m.dv);
+        if (m.lhs < (double)m.t) {
+            if (int rc = npt_rescale(c, m.w_new, &m.clamped)) return rc;
+            m.accepted = 1;
+        }
+    }
+    ++c->npt.trials;
+    c->npt.out_of_range += m.out_of_range;
+    if (m.accepted) {
+        ++c->npt.accepted;
+        c->npt.clamped += m.clamped;
+        c->npt.du_sum += m.du;
+    }
+    if (out) *out = m;
+    return PMC_OK;
+}
+
+int pmc_npt_stats_read(pmc_ctx* c, pmc_npt_stats* out, int reset) {
+    if (!c || !out) return fail(PMC_ERR_ARG, "bad argument");
+    *out = c->npt;
+    if (reset) std::memset(&c->npt, 0, sizeof(c->npt));
+    return PMC_OK;
+}
+
+int pmc_start_npt(pmc_ctx* c, uint32_t first, int mc_passes, int vol_every, float pressure, float dw_max, float w_min,
+                  float w_max, pmc_result* out, pmc_npt_stats* npt) {
+    if (!c || mc_passes < 0) return fail(PMC_ERR_ARG, "bad argument");
+    if (vol_every < 1) return fail(PMC_ERR_ARG, "pmc_start_npt: vol_every must be >= 1");
+    int rc = npt_args(c, "pmc_start_npt", pressure, dw_max, w_min, w_max);
+    if (rc) return rc;
+    pmc_result r;
+    std::memset(&r, 0, sizeof(r));
+    pmc_stats s0, s1;
+    pmc_npt_stats v;
+    std::memset(&v, 0, sizeof(v));
+    if ((rc = pmc_stats_read(c, &s0, 0)) || (rc = pmc_energy(c, &r.e_initial))) return rc;
+    PMC_HIP(hipEventRecord(c->ev0, c->stream));
+    for (int k = 0; k < mc_passes; ++k) {
+        const uint32_t s = first + (uint32_t)k;
+        if ((rc = enqueue_sweep(c, s))) return rc;
+        if ((s + 1u) % (uint32_t)vol_every != 0u) continue;
+        pmc_npt_move m;
+        if ((rc = pmc_volume_move(c, s, 0u, pressure, dw_max, w_min, w_max, &m))) return rc;
+        ++v.trials;
+        v.out_of_range += m.out_of_range;
+        if (m.accepted) {
+            ++v.accepted;
+            v.clamped += m.clamped;
+            v.du_sum += m.du;
+        }
+    }
+    PMC_HIP(hipEventRecord(c->ev1, c->stream));
+    PMC_HIP(hipEventSynchronize(c->ev1));
+    float ms = 0.0f;
+    PMC_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    r.seconds = ms * 1e-3;
+    if ((rc = pmc_energy(c, &r.e_final)) || (rc = pmc_stats_read(c, &s1, 0))) return rc;
+    r.stats.de_fixed = s1.de_fixed - s0.de_fixed;
+    r.stats.accepted = s1.accepted - s0.accepted;
+    r.stats.trials = s1.trials - s0.trials;
+    r.stats.evaluated = s1.evaluated - s0.evaluated;
+    r.sweeps = mc_passes;
+    uint32_t fl = 0;
+    if ((rc = pmc_error_flags(c, &fl, 0))) return rc;
+    if (out) *out = r;
+    if (npt) *npt = v;
     if (fl & 1u) return fail(PMC_ERR_OVERFLOW, "shiftCells: cell occupancy exceeded nmax");
     return PMC_OK;
 }

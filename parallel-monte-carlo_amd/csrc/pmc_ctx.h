@@ -41,6 +41,10 @@ struct pmc_ctx {
     int* boo_rec = nullptr;                    // storage_cells * nmax records of kBooRecord int32
     unsigned long long* boo_acc = nullptr;     // boo_acc_words(kBooMaxBins)
     unsigned long long* gc_acc = nullptr;      // exchange moves: accumulator copies (allocated on first use; kept until reset)
+    // volume moves: the pair-sum accumulator copies and the clamp counter (allocated on first use), and
+    // the host-side counters pmc_npt_stats_read returns
+    unsigned long long* npt_acc = nullptr;
+    pmc_npt_stats npt = {};
     uint32_t* flags = nullptr;
     int* ovf = nullptr;                   // subsweep overflow queue (1 + cells per colour)
     int* ovf_aux = nullptr;                // second queue: launches on a caller stream (pmc_phase_range_on)

@@ -165,6 +165,16 @@ constexpr int kPairObsMaxBins = 512;   // PMC_PAIROBS_MAX_BINS
 static_assert((kPairObsCopies & (kPairObsCopies - 1)) == 0, "accumulator copies: a power of two");
 hipError_t launch_pairobs(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc,
                           float rmax2, float bscale, int nbins, hipStream_t st);
+// volume moves (pmc_npt.h).  k_npt_sums: acc holds kNptCopies accumulator copies of the kNptHead
+// counters of pmc_npt_sums (in its order), zeroed on st before the call; the host sums the copies.
+// k_rescale: in place on a whole-box state, s = w_new / w; clamp_acc one counter, zeroed before.
+constexpr int kNptCopies = 32;
+constexpr int kNptHead = 4;
+static_assert((kNptCopies & (kNptCopies - 1)) == 0, "accumulator copies: a power of two");
+hipError_t launch_npt_sums(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc,
+                           hipStream_t st);
+hipError_t launch_rescale(const DevGeom& g, float* disk, const int16_t* n, float s, float w_new,
+                          unsigned long long* clamp_acc, hipStream_t st);
 // test-particle energies (k_probe, pmc_probe.h): acc holds kProbeCopies accumulator copies of
 // kProbeHead + 2 * nbins counters each ([0] probes, [1] overlaps, [2] below, [3] above, [4] pairs, then
 // hist[nbins], then esum[nbins]), zeroed on st before the call; the host sums the copies.  lo4 / bw4:

@@ -30,6 +30,7 @@
 #include "../../include/pmc_boo.h"
 #include "../../include/pmc_probe.h"
 #include "../../include/pmc_gc.h"
+#include "../../include/pmc_npt.h"
 #include "../../include/pmc_sk.h"
 #include "../../include/pmc_profile.h"
 #include "../../include/pmc_profile_ik.h"
@@ -2756,6 +2757,284 @@ __global__ __launch_bounds__(kWave) void k_pairobs(DevGeom g, const float* __res
 }
 
 // ------------------------------------------------------------------------------------------
+// isobaric volume moves (include/pmc_npt.h).
+//
+// k_npt_sums is k_pairobs' per-cell form without the histogram: the same stencil (pairobs_stencil),
+// the same staging (rows of 8 slots, chunks for the fuller cells, own cell first, the pmc_box_d2
+// filter and the 27 * nmax LDS capacity), the same ring of in-cutoff r2 values; a drained pair adds
+// fixed(r^-12) and fixed(r^-6) to two per-lane int64 sums.  A wave flushes once into one of
+// kNptCopies accumulator copies ([s12, s6, pairs, particles]) the host sums.  Integer sums only:
+// equal to tests/npt_ref.c bit for bit.
+// ------------------------------------------------------------------------------------------
+template <int NSLOT, bool OFF32>
+__global__ __launch_bounds__(kWave) void k_npt_sums(DevGeom g, const float* __restrict__ disk,
+                                                    const int16_t* __restrict__ ncnt,
+                                                    unsigned long long* __restrict__ acc, uint32_t total_cells) {
+    extern __shared__ __attribute__((aligned(16))) float psm[];
+    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
+    constexpr int CPP = kWave / HS;    // cells per staging pass
+    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
+    using DA = DiskAddr<OFF32>;
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int cap = 27 * nm;
+    float* ex_ = psm;
+    float* ey_ = psm + cap;
+    float* ez_ = psm + 2 * cap;
+    float* ring = psm + 3 * cap;
+    int* inv_l = (int*)(ring + kPairObsRing);      // list entry -> stencil lane (32 ints)
+    const int p = lane % HS;
+    const int ee = lane / HS;
+    const float rc2 = g.rc2;
+    long long sum12 = 0, sum6 = 0;                 // per lane
+    unsigned long long n_pairs = 0, n_part = 0;    // wave-uniform
+    if (lane < 32) inv_l[lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+
+    // rows of the cell in flight (k_pairobs' issue_rows): slots [0, HS) of its occupied stencil cells
+    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
+    bool vact[NPMAX];
+    int ncells = 0;
+    auto issue_rows = [&](const PairObsStencil& st) {
+        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
+        ncells = __popcll(mo);
+        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int q = 0; q < NPMAX; ++q) {
+            const int e = q * CPP + ee;
+            const int src = inv_l[e < ncells ? e : 0];
+            const int c_cnt = __shfl(st.cnt, src);
+            const int c_idx = __shfl(st.kc, src);
+            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
+            vact[q] = e < ncells && p < c_cnt;
+            vx[q] = vy[q] = vz[q] = 0.0f;
+            if (vact[q]) {
+                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
+                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
+                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
+                vy[q] = vy[q] + isy;
+                vz[q] = vz[q] + isz;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
+    };
+
+    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
+    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
+        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
+        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
+        issue_rows(cur);
+        PairObsStencil nxt = cur;
+        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
+        for (int c = 0; c < ncl; ++c) {
+            // ---- stage cell c (k_pairobs' staging): own particles first, then the filtered partners
+            float blo[3], bhi[3];
+            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
+            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
+            int S = 0;
+            auto put = [&](bool act, float ux, float uy, float uz) {
+                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+                if (act) {
+                    const int dst = S + mbcnt64(am);
+                    ex_[dst] = ux;
+                    ey_[dst] = uy;
+                    ez_[dst] = uz;
+                }
+                S += __popcll(am);
+            };
+            auto chunks = [&](unsigned long long mg, bool filter) {
+                if constexpr (NSLOT > HS) {
+                    for (int s0 = HS; s0 < nm; s0 += HS) {
+                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
+                        while (ov) {
+                            int ks = 0, nc = 0;
+                            for (; nc < CPP && ov; ++nc) {
+                                const int kb = (int)__builtin_ctzll(ov);
+                                ov &= ov - 1ull;
+                                ks = ee == nc ? kb : ks;
+                            }
+                            const int c_cnt = __shfl(cur.cnt, ks);
+                            const int c_idx = __shfl(cur.kc, ks);
+                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
+                            const int ps = s0 + p;
+                            const bool act = ee < nc && ps < c_cnt;
+                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+                            if (act) {
+                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
+                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+                                ux = ux + isx;
+                                uy = uy + isy;
+                                uz = uz + isz;
+                            }
+                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz);
+                        }
+                    }
+                }
+            };
+            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
+            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
+            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0]);             // own slots [0, HS)
+            chunks(1ull, false);                                          // own slots [HS, n)
+#pragma unroll
+            for (int q = 0; q < NPMAX; ++q) {
+                const int e = q * CPP + ee;
+                if (q * CPP < ncells) put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q]);
+            }
+            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            // ---- the next cell's rows go out now and arrive while this cell's pairs run
+            if (c + 1 < ncl) {
+                cur = nxt;
+                issue_rows(cur);
+                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
+            }
+            n_part += (unsigned long long)n_own;
+            if (n_own == 0) continue;
+            // ---- ordered pairs (i, j), k_pairobs' blocks and ring; j == i skipped
+            constexpr int RM = kPairObsRing - 1;
+            int head = 0, C = 0;   // ring: entries [head, head + C) mod kPairObsRing
+            auto drain = [&](int lim) {
+                if (lane < lim) {
+                    float p6, p12;
+                    pmc_npt_terms(ring[(head + lane) & RM], &p6, &p12);
+                    sum6 += pmc_to_fixed_f32(p6);
+                    sum12 += pmc_to_fixed_f32(p12);
+                }
+                head = (head + 64) & RM;
+                C -= lim;
+            };
+            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+            auto block = [&](int jb, auto first_c) {
+                constexpr bool kFirst = decltype(first_c)::value;
+                const int j = jb + lane;
+                const bool vj = j < S;
+                const int jj = vj ? j : 0;
+                float xj = ox, yj = oy, zj = oz;
+                if constexpr (!kFirst) {
+                    xj = ex_[jj];
+                    yj = ey_[jj];
+                    zj = ez_[jj];
+                }
+                const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
+                for (int i = 0; i < n_own; ++i) {
+                    const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+                    const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+                    const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+                    const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
+                    unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rc2) & vm;
+                    if constexpr (kFirst) im &= ~(1ull << i);
+                    if (__builtin_amdgcn_inverse_ballot_w64(im)) ring[(head + C + mbcnt64(im)) & RM] = r2;
+                    const int k = __popcll(im);
+                    C += k;   // C < 64 + 64 <= ring size
+                    n_pairs += (unsigned long long)k;
+                    if (C >= 64) drain(64);
+                }
+            };
+            block(0, std::true_type{});
+            for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
+            if (C > 0) drain(C);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+        }
+    }
+    // ---- flush: wave sums (int64, exact in any order)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sum12 += __shfl_xor(sum12, o);
+        sum6 += __shfl_xor(sum6, o);
+    }
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kNptCopies - 1)) * (size_t)kNptHead;
+    const unsigned long long head4 = lane == 0 ? (unsigned long long)sum12
+                                               : (lane == 1 ? (unsigned long long)sum6 : (lane == 2 ? n_pairs : n_part));
+    if (lane < kNptHead && head4 != 0) atomicAdd(&mine[lane], head4);
+}
+
+// k_rescale: the affine rescale of an accepted volume move, in place on the current buffer (whole
+// box).  One thread per granule of VEC floats of a cell's row; a granule that lies wholly inside the
+// occupied part of the row (packed layout: floats [0, 3 n); reference layout: [d * nmax, d * nmax + n)
+// of each dimension's row) moves as one 16-byte access, the granule that straddles its end by scalar
+// accesses up to the last occupied float, and a granule past it is neither read nor written: no slot
+// >= n[cell] is touched.  VEC = 4 needs nmax % 4 == 0 (then every row of 3 * nmax floats and, in the
+// reference layout, every dimension's row starts on 16 bytes); VEC = 1 otherwise.  Each coordinate:
+// pmc_npt_rescale_coord against its cell's new assign interval.  The clamps are counted per thread,
+// summed per block and added with one integer atomic.
+constexpr int kRescaleThreads = 256;
+
+template <bool OFF32>
+__device__ __forceinline__ float* rescale_at(float* b, uint32_t elem) {
+    if constexpr (OFF32) return (float*)((char*)b + (uint64_t)(elem * 4u));
+    else return b + (uint64_t)elem;
+}
+
+template <int VEC, bool OFF32>
+__global__ __launch_bounds__(kRescaleThreads) void k_rescale(DevGeom g, float* __restrict__ disk,
+                                                             const int16_t* __restrict__ ncnt, uint64_t total,
+                                                             UDivMagic div_gran, uint32_t gran_per_cell, float s,
+                                                             float w_new, unsigned long long* __restrict__ clamp_acc) {
+    __shared__ int part[kRescaleThreads / kWave];
+    const uint64_t gid64 = (uint64_t)blockIdx.x * kRescaleThreads + threadIdx.x;
+    int clamped = 0;
+    if (gid64 < total) {
+        const uint32_t gid = (uint32_t)gid64;
+        const uint32_t cell = udiv_magic(gid, div_gran);
+        const uint32_t e0 = (gid - cell * gran_per_cell) * (uint32_t)VEC;   // first float of the granule in the row
+        const int nm = g.nmax;
+        int n = (int)ncnt[cell];
+        n = n < 0 ? 0 : (n > nm ? nm : n);
+        // occupied floats of the granule: [e0, e1)
+        uint32_t e1;
+        if (PMC_AOS) {
+            e1 = (uint32_t)(3 * n);
+        } else {
+            const uint32_t d = e0 / (uint32_t)nm;   // (VEC = 4: nmax % 4 == 0, a granule stays in one row)
+            e1 = d * (uint32_t)nm + (uint32_t)n;
+        }
+        e1 = e1 < e0 + VEC ? e1 : e0 + VEC;
+        if (e1 > e0) {
+            // the cell and its new bounds per axis
+            const uint32_t q1 = udiv_magic(cell, g.div_cx);
+            const uint32_t zq = udiv_magic(cell, g.div_plane);
+            const int cc[3] = {(int)(cell - q1 * (uint32_t)g.cps_x), (int)(q1 - zq * (uint32_t)g.cps_y), g.z0 + (int)zq};
+            const float Ln[3] = {(float)g.cps_x * w_new, (float)g.cps_y * w_new, (float)g.cps_z * w_new};
+            float lo[3], hi[3];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                lo[d] = pmc_cell_lb(cc[d], w_new, Ln[d]);
+                hi[d] = pmc_cell_lb(cc[d] + 1, w_new, Ln[d]);
+            }
+            auto dim_of = [&](uint32_t e) { return PMC_AOS ? (int)(e % 3u) : (int)(e / (uint32_t)nm); };
+            auto scale = [&](float x, uint32_t e) {
+                const int d = dim_of(e);
+                const float l = d == 0 ? lo[0] : (d == 1 ? lo[1] : lo[2]);
+                const float h = d == 0 ? hi[0] : (d == 1 ? hi[1] : hi[2]);
+                return pmc_npt_rescale_coord(x, s, l, h, &clamped);
+            };
+            float* q = rescale_at<OFF32>(disk, cell * (uint32_t)(3 * nm) + e0);
+            if (VEC == 4 && e1 == e0 + 4u) {
+                float4 v = *reinterpret_cast<float4*>(q);
+                v.x = scale(v.x, e0);
+                v.y = scale(v.y, e0 + 1u);
+                v.z = scale(v.z, e0 + 2u);
+                v.w = scale(v.w, e0 + 3u);
+                *reinterpret_cast<float4*>(q) = v;
+            } else {
+                for (uint32_t e = e0; e < e1; ++e) q[e - e0] = scale(q[e - e0], e);
+            }
+        }
+    }
+    // clamp count: wave sum, block sum, one atomic
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) clamped += __shfl_xor(clamped, o);
+    if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = clamped;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int k = 0; k < kRescaleThreads / kWave; ++k) t += part[k];
+        if (t) atomicAdd(clamp_acc, (unsigned long long)t);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // cluster analysis (include/pmc_cluster.h): degrees, core particles and the connected components of
 // the core particles under "bonded in either direction", in four launches on one stream.
 //
@@ -5422,6 +5701,45 @@ hipError_t launch_pairobs(const DevGeom& g, const float* disk, const int16_t* n,
         constexpr bool O = decltype(off)::value;
         hipLaunchKernelGGL((k_pairobs<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, rmax2, bscale,
                            nbins);
+    });
+    return hipGetLastError();
+}
+
+// acc: kNptCopies copies of [s12, s6, pairs, particles], zeroed on st before the call.  launch_pairobs'
+// fixed grid; 5.8 KiB of LDS per wave at nmax 16 (no histogram).
+hipError_t launch_npt_sums(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc,
+                           hipStream_t st) {
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
+    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
+    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
+    const size_t lds = sizeof(float) * (3 * 27 * (size_t)g.nmax + kPairObsRing + 32);
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
+    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
+        hipLaunchKernelGGL((k_npt_sums<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total);
+    });
+    return hipGetLastError();
+}
+
+// In place on disk (whole box: storage cells = owned cells); g is the geometry BEFORE the move (only
+// its cell grid is read), s = w_new / w.  clamp_acc: one counter, zeroed on st before the call.
+// 16-byte granules when the rows allow (nmax % 4 == 0 and a 16-byte aligned buffer), single floats
+// otherwise; cells * 3 * nmax < 2^32 (pmc_create), so a granule index fits 32 bits.
+hipError_t launch_rescale(const DevGeom& g, float* disk, const int16_t* n, float s, float w_new,
+                          unsigned long long* clamp_acc, hipStream_t st) {
+    if (g.halo != 0) return hipErrorInvalidValue;
+    const int64_t cells = (int64_t)g.cps_x * g.cps_y * g.nz_local;
+    const bool vec = g.nmax % 4 == 0 && ((uintptr_t)disk & 15u) == 0;
+    const uint32_t gran = (uint32_t)(3 * g.nmax) / (vec ? 4u : 1u);
+    const uint64_t total = (uint64_t)cells * gran;
+    const dim3 grid((unsigned)((total + kRescaleThreads - 1) / kRescaleThreads)), block(kRescaleThreads);
+    const UDivMagic dg = make_udiv_magic(gran);
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
+    with_bool(!force64 && disk_off32(g), [&](auto off) {
+        constexpr bool O = decltype(off)::value;
+        if (vec) hipLaunchKernelGGL((k_rescale<4, O>), grid, block, 0, st, g, disk, n, total, dg, gran, s, w_new, clamp_acc);
+        else hipLaunchKernelGGL((k_rescale<1, O>), grid, block, 0, st, g, disk, n, total, dg, gran, s, w_new, clamp_acc);
     });
     return hipGetLastError();
 }

@@ -7,7 +7,7 @@
  *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS] [--widom K]
  *         [--sk HMAX] [--profile AXIS[:NBINS]] [--profile-ik AXIS[:NBINS]]
  *         [--gcmc Z [--gc-moves K] [--gc-every M]] [--clusters RB[:MINNB]]
- *         [--boo L:RB[:THRESH[:MINCONN]]]
+ *         [--boo L:RB[:THRESH[:MINCONN]]] [--npt P[:DW[:EVERY]] [--w-min W] [--w-max W]]
  *
  * --dump writes create_dump frames (kernel.cu:510-536; the reference's VISUALISATION path) of the
  * initial state and after every --every sweeps; --save writes a PMCSNAP1 snapshot at the end;
@@ -36,6 +36,13 @@
  * after every sweep s with (s + 1) % M == 0 (--gc-every, default 1) one exchange sweep of K insert /
  * delete attempts per cell and colour phase (--gc-moves, default 1).  Every report line then also
  * prints the particle number N and the interval's insert and delete acceptance; not with --graph.
+ *
+ * --npt P[:DW[:EVERY]] samples the isobaric ensemble at pressure P (pmc_start_npt): after every sweep s
+ * with (s + 1) % EVERY == 0 (default 1) one volume move, a uniform step of at most DW (default w / 100)
+ * in the cell width w, kept within [--w-min, --w-max] (default w / 2 and 2 w of the starting w).  The
+ * cutoff is w, so it scales with the box (pmc_npt.h).  Every report line then also prints N, w, the
+ * density rho and the interval's volume-move acceptance; not with --graph or --gcmc.  With --restart
+ * the context is created with the snapshot's w (the header is read first).
  *
  * --clusters RB[:MINNB] runs the cluster analysis (pmc_clusters: bond length RB <= w, a core particle
  * has at least MINNB bonds, default 0 = plain Stillinger clusters) with every report: one `clusters`
@@ -169,6 +176,8 @@ int main(int argc, char** argv) {
     int passes = 1000, every = 1, graph = 0, pairobs = 0, widom = 0, sk = 0, gc_moves = 1, gc_every = 1;
     int prof_axis = -1, prof_bins = 0, ik_axis = -1, ik_bins = 0;
     float gcmc = 0.0f, cl_rb = 0.0f;
+    int npt = 0, npt_every = 1;
+    float npt_p = 0.0f, npt_dw = 0.0f, w_min = 0.0f, w_max = 0.0f;
     int cl_minnb = 0, boo_l = 0, boo_c8 = 179, boo_minconn = 7;
     float boo_rb = 0.0f;
     const char *dump = NULL, *save = NULL, *restart = NULL;
@@ -237,6 +246,21 @@ int main(int argc, char** argv) {
             }
             ++i;
         }
+        else if (!strcmp(a, "--npt")) {
+            const char* c1 = strchr(v, ':');
+            const char* c2 = c1 ? strchr(c1 + 1, ':') : NULL;
+            npt = 1;
+            npt_p = (float)atof(v);
+            if (c1) npt_dw = (float)atof(c1 + 1);
+            if (c2) npt_every = atoi(c2 + 1);
+            if ((c1 && !(npt_dw > 0.0f)) || npt_every < 1) {
+                fprintf(stderr, "--npt P[:DW[:EVERY]]: DW > 0, EVERY >= 1\n");
+                return 2;
+            }
+            ++i;
+        }
+        else if (!strcmp(a, "--w-min")) { w_min = (float)atof(v); ++i; }
+        else if (!strcmp(a, "--w-max")) { w_max = (float)atof(v); ++i; }
         else if (!strcmp(a, "--gcmc")) { gcmc = (float)atof(v); ++i; }
         else if (!strcmp(a, "--gc-moves")) { gc_moves = atoi(v); ++i; }
         else if (!strcmp(a, "--gc-every")) { gc_every = atoi(v); ++i; }
@@ -245,9 +269,21 @@ int main(int argc, char** argv) {
     if (every < 1) every = 1;
     if (sk < 0 || sk > 1024) { fprintf(stderr, "--sk HMAX: 1..1024\n"); return 2; }
     if (gcmc != 0.0f && graph) { fprintf(stderr, "--gcmc cannot be combined with --graph\n"); return 2; }
+    if (npt && (graph || gcmc != 0.0f)) { fprintf(stderr, "--npt cannot be combined with --graph or --gcmc\n"); return 2; }
 
     pmc_ctx* ctx = NULL;
-    int rc = pmc_create(&p, &ctx);
+    int rc;
+    if (npt && restart) {   /* an isobaric run's snapshot holds its own w: pmc_load_snapshot refuses another */
+        pmc_params sp;
+        if ((rc = pmc_snapshot_read(restart, &sp, NULL, NULL, NULL, NULL, 0))) die("pmc_snapshot_read", rc);
+        p.w = sp.w;
+    }
+    if (npt) {
+        if (!(npt_dw > 0.0f)) npt_dw = p.w / 100.0f;
+        if (!(w_min > 0.0f)) w_min = p.w / 2.0f;
+        if (!(w_max > 0.0f)) w_max = p.w * 2.0f;
+    }
+    rc = pmc_create(&p, &ctx);
     if (rc) die("pmc_create", rc);
     uint32_t first = 0;
     if (restart) {
@@ -295,6 +331,21 @@ int main(int argc, char** argv) {
             printf("%u: %f N %lld insert %.6f delete %.6f\n", (unsigned)(s + (uint32_t)k), e, (long long)n_now,
                    g.ins_trials ? (double)g.ins_accepted / (double)g.ins_trials : 0.0,
                    g.del_trials ? (double)g.del_accepted / (double)g.del_trials : 0.0);
+        } else if (npt) {
+            pmc_npt_stats v;
+            pmc_params q;
+            int64_t n_now = 0;
+            if ((rc = pmc_start_npt(ctx, s, k, npt_every, npt_p, npt_dw, w_min, w_max, &r, &v))) die("pmc_start_npt", rc);
+            if ((rc = pmc_particle_count(ctx, &n_now)) || (rc = pmc_get_params(ctx, &q))) die("pmc_get_params", rc);
+            e = r.e_final;
+            seconds += r.seconds;
+            total.accepted += r.stats.accepted;
+            total.trials += r.stats.trials;
+            total.evaluated += r.stats.evaluated;
+            total.de_fixed += r.stats.de_fixed;
+            const double vol = (double)q.cps_x * q.cps_y * q.cps_z * (double)q.w * (double)q.w * (double)q.w;
+            printf("%u: %f N %lld w %.7f rho %.6f volume %.6f\n", (unsigned)(s + (uint32_t)k), e, (long long)n_now,
+                   (double)q.w, (double)n_now / vol, v.trials ? (double)v.accepted / (double)v.trials : 0.0);
         } else {
             /* energies once per interval (for the trace line), not around every pmc_start */
             if ((rc = pmc_start_ex(ctx, s, k, PMC_START_NO_ENERGY, &r))) die("pmc_start_ex", rc);
@@ -305,7 +356,7 @@ int main(int argc, char** argv) {
             total.evaluated += r.stats.evaluated;
             total.de_fixed += r.stats.de_fixed;
         }
-        if (gcmc == 0.0f) printf("%u: %f\n", (unsigned)(s + (uint32_t)k), e);
+        if (gcmc == 0.0f && !npt) printf("%u: %f\n", (unsigned)(s + (uint32_t)k), e);
         if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)(s + (uint32_t)k), cl_rb, cl_minnb, 0);
         if (boo_l) print_boo(ctx, (unsigned)(s + (uint32_t)k), boo_l, boo_rb, boo_c8, boo_minconn, 0);
         if (dump && (rc = pmc_dump_frame(ctx, dump, 1, (int64_t)(s + (uint32_t)k)))) die("pmc_dump_frame", rc);

@@ -87,6 +87,40 @@ class GcStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class NptSums(C.Structure):
+    """``pmc_npt_sums``."""
+
+    _fields_ = [(k, C.c_int64) for k in ("s12_fixed", "s6_fixed", "pairs", "particles")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class NptMove(C.Structure):
+    """``pmc_npt_move``."""
+
+    _fields_ = [("accepted", C.c_int32), ("out_of_range", C.c_int32), ("w_old", C.c_float), ("w_new", C.c_float),
+                ("t", C.c_float), ("pad_", C.c_int32), ("du", C.c_double), ("dv", C.c_double), ("lhs", C.c_double),
+                ("clamped", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+        d["accepted"], d["out_of_range"] = bool(d["accepted"]), bool(d["out_of_range"])
+        return d
+
+
+class NptStats(C.Structure):
+    """``pmc_npt_stats``."""
+
+    _fields_ = [("trials", C.c_int64), ("accepted", C.c_int64), ("out_of_range", C.c_int64), ("clamped", C.c_int64),
+                ("du_sum", C.c_double)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("trials", "accepted", "out_of_range", "clamped")}
+        d["du_sum"] = float(self.du_sum)
+        return d
+
+
 class Result(C.Structure):
     """``pmc_result``."""
 
@@ -213,6 +247,12 @@ def lib():
         _sig(L, "pmc_gc_stats_read", i32, _vp, C.POINTER(GcStats), i32)
         _sig(L, "pmc_particle_count", i32, _vp, C.POINTER(i64))
         _sig(L, "pmc_start_gc", i32, _vp, u32, i32, i32, C.c_float, i32, C.POINTER(Result), C.POINTER(GcStats))
+        f32 = C.c_float
+        _sig(L, "pmc_volume_sums", i32, _vp, C.POINTER(NptSums))
+        _sig(L, "pmc_rescale", i32, _vp, f32, C.POINTER(i64))
+        _sig(L, "pmc_volume_move", i32, _vp, u32, u32, f32, f32, f32, f32, C.POINTER(NptMove))
+        _sig(L, "pmc_npt_stats_read", i32, _vp, C.POINTER(NptStats), i32)
+        _sig(L, "pmc_start_npt", i32, _vp, u32, i32, i32, f32, f32, f32, f32, C.POINTER(Result), C.POINTER(NptStats))
         _sig(L, "pmc_stats_read", i32, _vp, C.POINTER(Stats), i32)
         _sig(L, "pmc_error_flags", i32, _vp, C.POINTER(C.c_uint32), i32)
         _sig(L, "pmc_copy_out", i32, _vp, _vp, _vp)

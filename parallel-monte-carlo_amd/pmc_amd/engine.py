@@ -22,8 +22,8 @@ from typing import Optional
 import numpy as np
 
 from ._lib import (PMC_BOO_CONN_BINS, PMC_BOO_RECORD, PMC_CLUSTER_DEG_BINS, PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT,
-                   PMC_PROBE_REAL, BooObs, ClusterObs, GcStats, PairObs, Params, ProbeObs, ProfileObs, Result, SkObs,
-                   Stats, check, lib)
+                   PMC_PROBE_REAL, BooObs, ClusterObs, GcStats, NptMove, NptStats, NptSums, PairObs, Params, ProbeObs,
+                   ProfileObs, Result, SkObs, Stats, check, lib)
 
 FIX_SCALE = 2.0 ** 32
 
@@ -312,6 +312,67 @@ class PmcContext:
                                                  C.byref(g)))
         out = r.stats.as_dict()
         out.update(e_initial=r.e_initial, e_final=r.e_final, seconds=r.seconds, sweeps=int(r.sweeps), gc=g.as_dict())
+        return out
+
+    # ---- isobaric volume moves (include/pmc_npt.h) -------------------------------------------
+    def _refresh_geometry(self) -> None:
+        """The wrapper's copies of the cell width (self.w, self.params.w) from the context's."""
+        self.params.w = self.get_params().w
+        self.w = float(self.params.w)
+
+    def volume_sums(self) -> dict:
+        """The fixed-point sums of r^-12 and r^-6 over the ordered pairs inside the cutoff, with pairs
+        and particles (pmc_volume_sums).  Integer sums: slab contexts add exactly.
+        observables.volume_energy gives U at any scale from them."""
+        s = NptSums()
+        check("pmc_volume_sums", lib().pmc_volume_sums(self._h, C.byref(s)))
+        return s.as_dict()
+
+    def rescale(self, w_new: float) -> int:
+        """The affine rescale of a whole-box context to the cell width w_new (pmc_rescale; the ratio
+        w_new / w within [7/8, 8/7]: compress a lattice start in several steps).  Returns the number of
+        coordinates clamped into their cell's new interval; self.w and self.params.w follow."""
+        cl = C.c_int64(0)
+        check("pmc_rescale", lib().pmc_rescale(self._h, w_new, C.byref(cl)))
+        self._refresh_geometry()
+        return int(cl.value)
+
+    def volume_move(self, s: int, pressure: float, dw_max: float, w_min: Optional[float] = None,
+                    w_max: Optional[float] = None, index: int = 0) -> dict:
+        """One volume move (sweep s, index) at the given pressure (pmc_volume_move): a uniform step of
+        at most dw_max in w, restricted to [w_min, w_max] (default w / 2 and 2 w of the current w).  Returns
+        the decision record: accepted, out_of_range, w_old, w_new, t, du, dv, lhs, clamped."""
+        m = NptMove()
+        lo = self.w / 2 if w_min is None else w_min
+        hi = self.w * 2 if w_max is None else w_max
+        check("pmc_volume_move", lib().pmc_volume_move(self._h, s & 0xFFFFFFFF, index & 0xFFFFFFFF, pressure, dw_max,
+                                                       lo, hi, C.byref(m)))
+        if m.accepted:
+            self._refresh_geometry()
+        return m.as_dict()
+
+    def npt_stats(self, reset: bool = False) -> dict:
+        """The accumulated volume-move counters (pmc_npt_stats); observables.npt_acceptance converts."""
+        st = NptStats()
+        check("pmc_npt_stats_read", lib().pmc_npt_stats_read(self._h, C.byref(st), int(reset)))
+        return st.as_dict()
+
+    def run_npt(self, first: int, passes: int, pressure: float, dw_max: float, w_min: Optional[float] = None,
+                w_max: Optional[float] = None, every: int = 1) -> dict:
+        """pmc_start_npt: `passes` sweeps from `first`, a volume move after every sweep s with
+        (s + 1) % every == 0.  Returns start()'s dict with the run's volume-move counters under "npt" and
+        the final cell width under "w"."""
+        r, st = Result(), NptStats()
+        lo = self.w / 2 if w_min is None else w_min
+        hi = self.w * 2 if w_max is None else w_max
+        try:
+            check("pmc_start_npt", lib().pmc_start_npt(self._h, first & 0xFFFFFFFF, passes, every, pressure, dw_max, lo,
+                                                       hi, C.byref(r), C.byref(st)))
+        finally:
+            self._refresh_geometry()
+        out = r.stats.as_dict()
+        out.update(e_initial=r.e_initial, e_final=r.e_final, seconds=r.seconds, sweeps=int(r.sweeps), npt=st.as_dict(),
+                   w=self.w)
         return out
 
     def run_small(self, first: int, count: int) -> None:

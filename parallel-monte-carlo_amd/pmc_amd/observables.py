@@ -138,6 +138,38 @@ def gc_acceptance(stats: dict) -> dict:
             "empty": stats["del_empty"] / dt if dt else 0.0}
 
 
+# ---- isobaric volume moves (PmcContext.volume_sums / volume_move / run_npt, include/pmc_npt.h) ----
+
+def npt_acceptance(stats: dict) -> dict:
+    """Ratios of the volume-move counters (PmcContext.npt_stats or run_npt()["npt"]): accepted moves /
+    trials, the fraction of trials whose width left [w_min, w_max], and the clamped coordinates per
+    accepted move (all 0.0 when there was none)."""
+    t, a = int(stats["trials"]), int(stats["accepted"])
+    return {"volume": a / t if t else 0.0, "out_of_range": stats["out_of_range"] / t if t else 0.0,
+            "clamped_per_move": stats["clamped"] / a if a else 0.0}
+
+
+def box_volume(params) -> float:
+    """cps_x * cps_y * cps_z * w^3 of a pmc_params mirror (PmcContext.get_params(); the zero defaults of
+    cps_y and cps_z resolved), with w the float32 width as a double."""
+    cx = int(params.cps_x)
+    cy, cz = int(params.cps_y) or cx, int(params.cps_z) or cx
+    return cx * cy * cz * float(np.float32(params.w)) ** 3
+
+
+def density(n: int, params) -> float:
+    """Number density n / box_volume(params)."""
+    return n / box_volume(params)
+
+
+def volume_energy(sums: dict, q: float = 1.0) -> float:
+    """pmc_npt.h's U(q) = 2 (S12 q^12 - S6 q^6) from PmcContext.volume_sums' integers, in float64:
+    the energy of the configuration scaled to the cell width w / q (the cutoff scaling along).  q = 1 is
+    the current energy, equal to PmcContext.energy() up to one fixed-point rounding per pair."""
+    q = float(q)
+    return 2.0 * (float(sums["s12_fixed"]) * q ** 12 - float(sums["s6_fixed"]) * q ** 6) / FIX_SCALE
+
+
 # ---- density modes and S(k) (PmcContext.density_modes, include/pmc_sk.h) ------------------------
 
 def wave_vectors(h_max: int, half_space: bool = True) -> np.ndarray:
