@@ -497,6 +497,31 @@ typedef struct pmc_boo_obs {
 } pmc_boo_obs;
 int pmc_bond_order(pmc_ctx* ctx, int l, float r_bond, int c8, int min_conn, int nq, int nbins, uint64_t* h_q,
                    uint64_t* h_conn, uint64_t* h_size, int32_t* h_record, int32_t* h_label, pmc_boo_obs* out);
+/* Neighbour-averaged bond order (Lechner and Dellago) of the owned cells' particles, defined bit for bit
+ * in pmc_boo_avg.h: q-bar_l(i) = NA_l(i) / ((deg(i) + 1) * 16 * K_l) for l = 4 and l = 6, the norm of the
+ * sum over i and its bonded partners of their normalised harmonic sums u_m = Q_m * 16 / deg (pmc_boo.h's
+ * walk, bonds and Q_m).  The (q-bar_4, q-bar_6) plane separates liquid, bcc, hcp and fcc where the plain
+ * q_l of pmc_bond_order overlap.  The reference has no such observable.  All pointers are HOST pointers.
+ * h_qa4[nq], h_qa6[nq]: bin min(nq - 1, nq * NA / ((deg + 1) * 16 * K_l)) counts the particles with that
+ * q-bar_l (deg = 0 counts in out->isolated instead and enters no histogram).  h_joint[n2 * n2]: entry
+ * bin4 * n2 + bin6 with the same bins at n2 per axis.  h_slot (may be NULL): storage_cells * nmax entries
+ * of 4 int32 in slot order: NA4, NA6, deg, 0; zeros in empty slots.
+ * PMC_ERR_ARG (outputs untouched) for a null h_qa4, h_qa6, h_joint or out, r_bond not finite, <= 0 or
+ * > w, nq outside 1..4096, n2 outside 1..64, storage_cells * nmax >= 2^31, and for any slab context
+ * (halo != 0): the sums need the halo partners' u_m, which no rank holds.  Runs on the context stream
+ * and synchronises; state, statistics, exchange counters, error flags and the energy are left unchanged.
+ * Device scratch (pmc_bond_order's 64 bytes per slot, which the two calls share, plus 16 bytes per slot)
+ * is allocated on the first call and freed by pmc_destroy; a failed allocation returns PMC_ERR_HIP and
+ * leaves the context usable. */
+typedef struct pmc_boo_avg_obs {
+    int64_t particles;      /* particles in owned cells */
+    int64_t bonds;          /* ordered pairs with r2 <= rb2 (the sum of the degrees) */
+    int64_t isolated;       /* particles with deg = 0 (in no histogram) */
+    int64_t na_sum4;        /* sum over particles of NA4 */
+    int64_t na_sum6;        /* sum over particles of NA6 */
+} pmc_boo_avg_obs;
+int pmc_bond_order_avg(pmc_ctx* ctx, float r_bond, int nq, int n2, uint64_t* h_qa4, uint64_t* h_qa6, uint64_t* h_joint,
+                       int32_t* h_slot, pmc_boo_avg_obs* out);
 /* ---- grand-canonical exchange moves (mu V T) ------------------------------------------------
  * Insertions and deletions as a further kind of colour phase, defined bit for bit in pmc_gc.h: every
  * owned cell of the colour runs k_per_cell (1..64) attempts in order on its own particle list, each

@@ -15,6 +15,7 @@
 #include "../../include/pmc_pairobs.h"
 #include "../../include/pmc_cluster.h"
 #include "../../include/pmc_boo.h"
+#include "../../include/pmc_boo_avg.h"
 #include "../../include/pmc_probe.h"
 #include "../../include/pmc_gc.h"
 #include "../../include/pmc_npt.h"
@@ -29,6 +30,9 @@ static_assert(kClusterMaxBins == PMC_CLUSTER_MAX_BINS && kClusterDegBins == PMC_
 static_assert(kBooMaxBins == PMC_BOO_MAX_BINS && kBooConnBins == PMC_BOO_CONN_BINS && kBooRecord == PMC_BOO_RECORD &&
                   kBooQsum + PMC_BOO_TERMS <= kBooHead && kBooOwn >= PMC_BOO_TERMS + 1,
               "bond-orientational order: bin caps and record size");
+static_assert(kBooAvgMaxBins == PMC_BOO_AVG_MAX_BINS && kBooAvgMaxJoint == PMC_BOO_AVG_MAX_JOINT &&
+                  kBooAvgSlot == PMC_BOO_AVG_SLOT,
+              "averaged bond order: bin caps and per-slot size");
 static_assert(kProbeMaxBins == PMC_PROBE_MAX_BINS, "test-particle energies: bin cap");
 static_assert(kSkMaxK == PMC_SK_MAX_K, "density modes: vector cap");
 static_assert(kGcCounters == PMC_GC_COUNTERS && sizeof(pmc_gc_stats) == 8 * PMC_GC_COUNTERS, "exchange moves: counters");
@@ -321,7 +325,7 @@ void pmc_destroy(pmc_ctx* c) {
     if (c->gc_acc) (void)hipFree(c->gc_acc);
     if (c->npt_acc) (void)hipFree(c->npt_acc);
     for (void* m : {(void*)c->cl_parent, (void*)c->cl_size, (void*)c->cl_deg, (void*)c->cl_acc, (void*)c->boo_rec,
-                    (void*)c->boo_acc})
+                    (void*)c->boo_acc, (void*)c->boo_avg_slot, (void*)c->boo_avg_acc})
         if (m) (void)hipFree(m);
     if (c->flags) (void)hipFree(c->flags);
     if (c->ovf) (void)hipFree(c->ovf);
@@ -782,6 +786,21 @@ int pmc_clusters(pmc_ctx* c, float r_bond, int min_neighbours, int nbins, uint64
     return PMC_OK;
 }
 
+// pmc_bond_order's own device scratch (shared with pmc_bond_order_avg): both buffers or none
+static int boo_scratch(pmc_ctx* c, size_t slots, const char* what) {
+    if (c->boo_acc) return PMC_OK;
+    hipError_t e = hipMalloc(&c->boo_rec, sizeof(int32_t) * kBooRecord * slots);
+    if (e == hipSuccess) e = hipMalloc(&c->boo_acc, sizeof(unsigned long long) * boo_acc_words(kBooMaxBins));
+    if (e != hipSuccess) {
+        if (c->boo_rec) (void)hipFree(c->boo_rec);
+        c->boo_rec = nullptr;
+        c->boo_acc = nullptr;
+        (void)hipGetLastError();   // the context stays usable
+        return hip_fail(e, what);
+    }
+    return PMC_OK;
+}
+
 int pmc_bond_order(pmc_ctx* c, int l, float r_bond, int c8, int min_conn, int nq, int nbins, uint64_t* h_q,
                    uint64_t* h_conn, uint64_t* h_size, int32_t* h_record, int32_t* h_label, pmc_boo_obs* out) {
     if (!c || !h_q || !h_conn || !h_size || !out) return fail(PMC_ERR_ARG, "bad argument");
@@ -800,18 +819,7 @@ int pmc_bond_order(pmc_ctx* c, int l, float r_bond, int c8, int min_conn, int nq
     const size_t slots = (size_t)slots64;
     if (int rj = slab_join(c)) return rj;
     if (int ra = cluster_scratch(c, slots, "pmc_bond_order: scratch allocation")) return ra;
-    if (!c->boo_acc) {
-        // both or none
-        hipError_t e = hipMalloc(&c->boo_rec, sizeof(int32_t) * kBooRecord * slots);
-        if (e == hipSuccess) e = hipMalloc(&c->boo_acc, sizeof(unsigned long long) * boo_acc_words(kBooMaxBins));
-        if (e != hipSuccess) {
-            if (c->boo_rec) (void)hipFree(c->boo_rec);
-            c->boo_rec = nullptr;
-            c->boo_acc = nullptr;
-            (void)hipGetLastError();   // the context stays usable
-            return hip_fail(e, "pmc_bond_order: scratch allocation");
-        }
-    }
+    if (int ra = boo_scratch(c, slots, "pmc_bond_order: scratch allocation")) return ra;
     const size_t cwords = cluster_acc_words(nbins), bwords = boo_acc_words(nq);
     PMC_HIP(hipMemsetAsync(c->cl_parent, 0xFF, sizeof(int) * slots, c->stream));
     PMC_HIP(hipMemsetAsync(c->cl_size, 0, sizeof(unsigned) * slots, c->stream));
@@ -854,6 +862,61 @@ int pmc_bond_order(pmc_ctx* c, int l, float r_bond, int c8, int min_conn, int nq
     for (int b = 0; b < PMC_BOO_CONN_BINS; ++b) h_conn[b] = (uint64_t)s[(size_t)kBooHead + (size_t)b];
     for (int b = 0; b < nq; ++b) h_q[b] = (uint64_t)s[(size_t)kBooHead + kBooConnBins + (size_t)b];
     for (int b = 0; b < nbins; ++b) h_size[b] = (uint64_t)tail[(size_t)kClusterTail + (size_t)b];
+    return PMC_OK;
+}
+
+int pmc_bond_order_avg(pmc_ctx* c, float r_bond, int nq, int n2, uint64_t* h_qa4, uint64_t* h_qa6, uint64_t* h_joint,
+                       int32_t* h_slot, pmc_boo_avg_obs* out) {
+    if (!c || !h_qa4 || !h_qa6 || !h_joint || !out) return fail(PMC_ERR_ARG, "bad argument");
+    if (c->P.halo != 0)
+        return fail(PMC_ERR_ARG, "pmc_bond_order_avg: whole-box contexts only (halo == 0): the averaged sums need the "
+                                 "normalised harmonics u_m of the halo partners, which no rank holds");
+    if (!std::isfinite(r_bond) || !(r_bond > 0.0f) || r_bond > c->P.w)
+        return fail(PMC_ERR_ARG, "pmc_bond_order_avg: r_bond must be finite, > 0 and <= w");
+    if (nq < 1 || nq > PMC_BOO_AVG_MAX_BINS) return fail(PMC_ERR_ARG, "pmc_bond_order_avg: nq must be in 1..4096");
+    if (n2 < 1 || n2 > PMC_BOO_AVG_MAX_JOINT) return fail(PMC_ERR_ARG, "pmc_bond_order_avg: n2 must be in 1..64");
+    const int64_t slots64 = c->cells * (int64_t)c->P.nmax;
+    if (slots64 >= ((int64_t)1 << 31)) return fail(PMC_ERR_ARG, "pmc_bond_order_avg: storage_cells * nmax must be below 2^31");
+    const size_t slots = (size_t)slots64;
+    if (int rj = slab_join(c)) return rj;
+    if (int ra = boo_scratch(c, slots, "pmc_bond_order_avg: scratch allocation")) return ra;
+    if (!c->boo_avg_acc) {
+        // both or none
+        hipError_t e = hipMalloc(&c->boo_avg_slot, sizeof(int32_t) * kBooAvgSlot * slots);
+        if (e == hipSuccess)
+            e = hipMalloc(&c->boo_avg_acc, sizeof(unsigned long long) * boo_avg_words(kBooAvgMaxBins, kBooAvgMaxJoint));
+        if (e != hipSuccess) {
+            if (c->boo_avg_slot) (void)hipFree(c->boo_avg_slot);
+            c->boo_avg_slot = nullptr;
+            c->boo_avg_acc = nullptr;
+            (void)hipGetLastError();   // the context stays usable
+            return hip_fail(e, "pmc_bond_order_avg: scratch allocation");
+        }
+    }
+    const size_t words = boo_avg_words(nq, n2), per = boo_avg_stride(nq, n2);
+    PMC_HIP(hipMemsetAsync(c->boo_avg_acc, 0, sizeof(unsigned long long) * words, c->stream));
+    hipError_t e = launch_bond_order_avg(c->G, c->disk[c->cur], c->n[c->cur], pmc_cutoff_r2(r_bond), nq, n2, c->boo_rec,
+                                         c->boo_avg_slot, c->boo_acc, c->boo_avg_acc, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "averaged bond-order analysis launch");
+    std::vector<unsigned long long> h(words);
+    PMC_HIP(hipMemcpyAsync(h.data(), c->boo_avg_acc, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, c->stream));
+    if (h_slot)
+        PMC_HIP(hipMemcpyAsync(h_slot, c->boo_avg_slot, sizeof(int32_t) * kBooAvgSlot * slots, hipMemcpyDeviceToHost,
+                               c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    std::vector<unsigned long long> s(per, 0ull);
+    for (int k = 0; k < kBooAvgCopies; ++k)
+        for (size_t i = 0; i < per; ++i) s[i] += h[(size_t)k * per + i];
+    out->bonds = (int64_t)s[0];
+    out->particles = (int64_t)s[1];
+    out->isolated = (int64_t)s[2];
+    out->na_sum4 = (int64_t)s[3];
+    out->na_sum6 = (int64_t)s[4];
+    for (int b = 0; b < nq; ++b) {
+        h_qa4[b] = (uint64_t)s[(size_t)kBooAvgHead + (size_t)b];
+        h_qa6[b] = (uint64_t)s[(size_t)kBooAvgHead + (size_t)nq + (size_t)b];
+    }
+    for (int b = 0; b < n2 * n2; ++b) h_joint[b] = (uint64_t)s[(size_t)kBooAvgHead + 2 * (size_t)nq + (size_t)b];
     return PMC_OK;
 }
 

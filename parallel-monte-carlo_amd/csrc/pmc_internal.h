@@ -262,6 +262,26 @@ constexpr size_t boo_acc_words(int nq) { return (size_t)kBooCopies * boo_acc_str
 hipError_t launch_bond_order(const DevGeom& g, const float* disk, const int16_t* n, int l, float rb2, int c8,
                              int min_conn, int nq, int nbins, int* rec, int* parent, unsigned* size, uint16_t* nconn,
                              unsigned long long* boo_acc, unsigned long long* cl_acc, hipStream_t st);
+// neighbour-averaged bond order (pmc_boo_avg.h) of a whole-box context with slots = cells * nmax < 2^31:
+// per l in 4, 6: k_boo_accum<.., l> (its accumulators go to boo_scratch, boo_acc_words(1) counters that
+// nobody reads), k_boo_unit (Q_m -> u_m in rec, in place) and k_boo_avg<.., l>; then k_boo_joint.  rec:
+// launch_bond_order's record scratch.  slot: kBooAvgSlot int32 per slot (NA4, NA6, deg, 0), every slot
+// written by the call.  acc, zeroed on st before the call: kBooAvgCopies copies of boo_avg_stride(nq, n2)
+// counters the host sums: [0] ordered bonds, [1] owned particles, [2] particles without a bond, [3] the
+// sum of NA4, [4] the sum of NA6, then from kBooAvgHead h_qa4[nq], h_qa6[nq] and h_joint[n2 * n2].
+constexpr int kBooAvgCopies = 32;
+constexpr int kBooAvgHead = 8;
+constexpr int kBooAvgSlot = 4;           // PMC_BOO_AVG_SLOT
+constexpr int kBooAvgMaxBins = 4096;     // PMC_BOO_AVG_MAX_BINS
+constexpr int kBooAvgMaxJoint = 64;      // PMC_BOO_AVG_MAX_JOINT
+static_assert((kBooAvgCopies & (kBooAvgCopies - 1)) == 0, "accumulator copies: a power of two");
+__host__ __device__ constexpr size_t boo_avg_stride(int nq, int n2) {
+    return (size_t)kBooAvgHead + 2 * (size_t)nq + (size_t)n2 * (size_t)n2;
+}
+constexpr size_t boo_avg_words(int nq, int n2) { return (size_t)kBooAvgCopies * boo_avg_stride(nq, n2); }
+hipError_t launch_bond_order_avg(const DevGeom& g, const float* disk, const int16_t* n, float rb2, int nq, int n2,
+                                 int* rec, int* slot, unsigned long long* boo_scratch, unsigned long long* acc,
+                                 hipStream_t st);
 // the cells of one colour of one plane: mode 0 plane -> packed buffer, 1 packed -> plane,
 // 2 plane -> plane; (cps_x/2)*(cps_y/2)*3*nmax floats
 hipError_t launch_colour_rows(const DevGeom& g, const float* src, float* dst, int colour, int mode, hipStream_t st);

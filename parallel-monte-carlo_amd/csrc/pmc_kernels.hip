@@ -28,6 +28,7 @@
 #include "../../include/pmc_pairobs.h"
 #include "../../include/pmc_cluster.h"
 #include "../../include/pmc_boo.h"
+#include "../../include/pmc_boo_avg.h"
 #include "../../include/pmc_probe.h"
 #include "../../include/pmc_gc.h"
 #include "../../include/pmc_npt.h"
@@ -3700,6 +3701,329 @@ __global__ __launch_bounds__(kWave) void k_boo_conn(DevGeom g, const float* __re
 }
 
 // ------------------------------------------------------------------------------------------
+// neighbour-averaged bond order (include/pmc_boo_avg.h): per l, k_boo_accum<.., L> (unchanged) fills
+// the record scratch, k_boo_unit replaces Q_m by u_m in place, and k_boo_avg<.., L> sums u_m over
+// every particle's first shell; k_boo_joint then bins the pairs (q-bar_4, q-bar_6).
+//
+// k_boo_unit: one thread per slot below its cell's count.  The truncating division by deg happens
+// here, once per particle: on a hit it would be repeated once per bond (12 times at r_bond 1.5) for
+// 2l + 1 values, about 25 instructions each.  The dividend Q_m * 16 fits int32 (pmc_boo_avg.h), and
+// the 32-bit signed division of C truncates toward zero: the quotient of the definition, exactly.  In
+// place: the analysis has no further use for Q_m, and a second record scratch would cost another 64
+// bytes per slot.  N and deg stay where they are.
+//
+// k_boo_avg<.., L>: k_boo_conn's form (boo_walk's stencil, staging, chunks, pmc_box_d2 filter; every
+// staged particle carries its id).  The blocks of partners without a hit are skipped wave-uniformly;
+// on a hit the lane gathers the partner's u by id (2l + 1 ints of its 64-byte record) and adds them
+// to the LDS table [own slot][2l + 1] with LDS integer atomics (the hit lanes of one own particle
+// share its row, as in k_boo_accum: integer sums do not depend on the order in which the adds
+// land).  Lane i then adds its own u_m(i), forms
+// NA by pmc_boo_isqrt64, writes its word of the compact per-slot array (l = 4: the whole 16 bytes,
+// NA4, 0, deg, 0, zeros between the count and nmax and in empty cells, so nothing needs a memset;
+// l = 6: NA6 alone) and bins q-bar_l in the wave's LDS histogram.
+// acc: kBooAvgCopies copies of boo_avg_stride(nq, n2) counters (pmc_internal.h).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_boo_unit(const int16_t* __restrict__ ncnt, int* __restrict__ rec,
+                                                  uint32_t slots, uint32_t nmax) {
+    const uint32_t nthreads = gridDim.x * blockDim.x;
+    for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < slots; id += nthreads) {
+        const uint32_t cell = id / nmax;
+        if ((int)(id - cell * nmax) >= (int)ncnt[cell]) continue;
+        int4* r4 = (int4*)(rec + (size_t)id * kBooRecord);
+        int4 a = r4[0], b = r4[1], cc = r4[2], d = r4[3];
+        const int deg = d.z;
+        a.x = pmc_boo_avg_unit(a.x, deg); a.y = pmc_boo_avg_unit(a.y, deg);
+        a.z = pmc_boo_avg_unit(a.z, deg); a.w = pmc_boo_avg_unit(a.w, deg);
+        b.x = pmc_boo_avg_unit(b.x, deg); b.y = pmc_boo_avg_unit(b.y, deg);
+        b.z = pmc_boo_avg_unit(b.z, deg); b.w = pmc_boo_avg_unit(b.w, deg);
+        cc.x = pmc_boo_avg_unit(cc.x, deg); cc.y = pmc_boo_avg_unit(cc.y, deg);
+        cc.z = pmc_boo_avg_unit(cc.z, deg); cc.w = pmc_boo_avg_unit(cc.w, deg);
+        d.x = pmc_boo_avg_unit(d.x, deg);
+        r4[0] = a;
+        r4[1] = b;
+        r4[2] = cc;
+        r4[3] = d;
+    }
+}
+
+template <int NSLOT, bool OFF32, int L>
+__global__ __launch_bounds__(kWave) void k_boo_avg(DevGeom g, const float* __restrict__ disk,
+                                                   const int16_t* __restrict__ ncnt,
+                                                   unsigned long long* __restrict__ acc, uint32_t total_cells,
+                                                   float rb2, int nq, int n2, const int* __restrict__ rec,
+                                                   int* __restrict__ slot_out) {
+    static_assert(L == 4 || L == 6, "l is 4 or 6");
+    extern __shared__ __attribute__((aligned(16))) float csm[];
+    constexpr int NT = 2 * L + 1;      // ints per own particle in the LDS table
+    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
+    constexpr int CPP = kWave / HS;    // cells per staging pass
+    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
+    using DA = DiskAddr<OFF32>;
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int cap = 27 * nm;
+    float* ex_ = csm;
+    float* ey_ = csm + cap;
+    float* ez_ = csm + 2 * cap;
+    int* et_ = (int*)(csm + 3 * cap);              // id of a staged particle
+    int* inv_l = et_ + cap;                        // list entry -> stencil lane (32 ints)
+    int* tab = inv_l + 32;                         // [kWave][NT]: A_m of the own particles
+    unsigned* hist = (unsigned*)(tab + kWave * NT);   // nq bins of q-bar_l
+    const int p = lane % HS;
+    const int ee = lane / HS;
+    unsigned long long n_pairs = 0, n_part = 0;    // wave-uniform
+    for (int b = lane; b < nq; b += kWave) hist[b] = 0u;
+    if (lane < 32) inv_l[lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+
+    // rows of the cell in flight (boo_walk's issue_rows): slots [0, HS) of its occupied stencil cells
+    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
+    int vt[NPMAX];
+    bool vact[NPMAX];
+    int ncells = 0;
+    auto issue_rows = [&](const PairObsStencil& st) {
+        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
+        ncells = __popcll(mo);
+        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int q = 0; q < NPMAX; ++q) {
+            const int e = q * CPP + ee;
+            const int src = inv_l[e < ncells ? e : 0];
+            const int c_cnt = __shfl(st.cnt, src);
+            const int c_idx = __shfl(st.kc, src);
+            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
+            vact[q] = e < ncells && p < c_cnt;
+            vx[q] = vy[q] = vz[q] = 0.0f;
+            vt[q] = -1;
+            if (vact[q]) {
+                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
+                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
+                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
+                vy[q] = vy[q] + isy;
+                vz[q] = vz[q] + isz;
+                vt[q] = c_idx * nm + p;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
+    };
+
+    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
+    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
+        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
+        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
+        issue_rows(cur);
+        PairObsStencil nxt = cur;
+        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
+        for (int c = 0; c < ncl; ++c) {
+            // ---- stage cell c (boo_walk's staging): own particles first, then the filtered partners
+            float blo[3], bhi[3];
+            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
+            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
+            int S = 0;
+            auto put = [&](bool act, float ux, float uy, float uz, int ut) {
+                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+                if (act) {
+                    const int dst = S + mbcnt64(am);
+                    ex_[dst] = ux;
+                    ey_[dst] = uy;
+                    ez_[dst] = uz;
+                    et_[dst] = ut;
+                }
+                S += __popcll(am);
+            };
+            // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles
+            auto chunks = [&](unsigned long long mg, bool filter) {
+                if constexpr (NSLOT > HS) {
+                    for (int s0 = HS; s0 < nm; s0 += HS) {
+                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
+                        while (ov) {
+                            int ks = 0, nc = 0;
+                            for (; nc < CPP && ov; ++nc) {
+                                const int kb = (int)__builtin_ctzll(ov);
+                                ov &= ov - 1ull;
+                                ks = ee == nc ? kb : ks;
+                            }
+                            const int c_cnt = __shfl(cur.cnt, ks);
+                            const int c_idx = __shfl(cur.kc, ks);
+                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
+                            const int ps = s0 + p;
+                            const bool act = ee < nc && ps < c_cnt;
+                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+                            int ut = -1;
+                            if (act) {
+                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
+                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+                                ux = ux + isx;
+                                uy = uy + isy;
+                                uz = uz + isz;
+                                ut = c_idx * nm + ps;
+                            }
+                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz, ut);
+                        }
+                    }
+                }
+            };
+            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
+            const int id0 = __builtin_amdgcn_readfirstlane(cur.kc) * nm;  // id of the own cell's slot 0
+            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
+            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0], vt[0]);      // own slots [0, HS)
+            chunks(1ull, false);                                          // own slots [HS, n)
+#pragma unroll
+            for (int q = 0; q < NPMAX; ++q) {
+                const int e = q * CPP + ee;
+                if (q * CPP < ncells)
+                    put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q], vt[q]);
+            }
+            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
+            // ---- the own particles' table, zeroed
+            const bool own = lane < n_own;
+            for (int k = lane; k < n_own * NT; k += kWave) tab[k] = 0;
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            // ---- the next cell's rows go out now and arrive while this cell's pairs run
+            if (c + 1 < ncl) {
+                cur = nxt;
+                issue_rows(cur);
+                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
+            }
+            n_part += (unsigned long long)n_own;
+            if (n_own == 0) {
+                if constexpr (L == 4) {
+                    if (lane < nm) *(int4*)(slot_out + (size_t)(id0 + lane) * kBooAvgSlot) = make_int4(0, 0, 0, 0);
+                }
+                continue;
+            }
+            // ---- ordered pairs (i, j): lane j holds staged partner j (blocks of 64), own particle
+            //      i (staged first, in slot order: lane i of block 0) broadcast by readlane; j == i skipped
+            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+            const int ot = et_[lane];
+            int mydeg = 0;                                                 // lane i: deg(i)
+            auto block = [&](int jb, auto first_c) {
+                constexpr bool kFirst = decltype(first_c)::value;
+                const int j = jb + lane;
+                const bool vj = j < S;
+                const int jj = vj ? j : 0;
+                float xj = ox, yj = oy, zj = oz;
+                int tj = ot;
+                if constexpr (!kFirst) {
+                    xj = ex_[jj];
+                    yj = ey_[jj];
+                    zj = ez_[jj];
+                    tj = et_[jj];
+                }
+                const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
+                for (int i = 0; i < n_own; ++i) {
+                    const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+                    const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+                    const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+                    const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
+                    unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rb2) & vm;
+                    if constexpr (kFirst) im &= ~(1ull << i);
+                    if (im == 0ull) continue;   // wave-uniform
+                    if ((im >> lane) & 1ull) {
+                        // a hit lane holds a staged particle: tj is the id of a slot below its cell's count
+                        const int* rj = rec + (size_t)tj * kBooRecord;
+                        const int4* r4 = (const int4*)rj;
+                        const int4 a = r4[0], b = r4[1];
+                        int u[PMC_BOO_TERMS] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, rj[8], 0, 0, 0, 0};
+                        if constexpr (L == 6) {
+                            u[9] = rj[9];
+                            u[10] = rj[10];
+                            u[11] = rj[11];
+                            u[12] = rj[12];
+                        }
+                        int* row = tab + i * NT;
+#pragma unroll
+                        for (int m = 0; m < NT; ++m)
+                            (void)__hip_atomic_fetch_add(row + m, u[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    const int k = __popcll(im);
+                    n_pairs += (unsigned long long)k;
+                    mydeg += lane == i ? k : 0;
+                }
+            };
+            block(0, std::true_type{});
+            for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the table's atomics have landed
+            int na = 0;
+            if (own) {
+                const int* ri = rec + (size_t)(id0 + lane) * kBooRecord;
+                int32_t A[PMC_BOO_TERMS];
+#pragma unroll
+                for (int m = 0; m < PMC_BOO_TERMS; ++m) A[m] = m < NT ? tab[lane * NT + m] + ri[m] : 0;
+                na = (int)pmc_boo_avg_norm(A);
+                if (mydeg > 0)
+                    (void)__hip_atomic_fetch_add(&hist[pmc_boo_avg_bin((int64_t)na, mydeg, L, nq)], 1u, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            if (lane < nm) {
+                int* so = slot_out + (size_t)(id0 + lane) * kBooAvgSlot;
+                if constexpr (L == 4) *(int4*)so = make_int4(na, 0, own ? mydeg : 0, 0);
+                else so[1] = na;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_ and tab
+        }
+    }
+    // ---- flush into this wave's accumulator copy: the l = 4 pass counts the bonds and the particles
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kBooAvgCopies - 1)) * boo_avg_stride(nq, n2);
+    if constexpr (L == 4) {
+        const unsigned long long head2 = lane == 0 ? n_pairs : n_part;
+        if (lane < 2 && head2 != 0) atomicAdd(&mine[lane], head2);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    unsigned long long* gh = mine + kBooAvgHead + (L == 4 ? 0 : nq);
+    for (int b = lane; b < nq; b += kWave) {
+        const unsigned h = hist[b];
+        if (h) atomicAdd(&gh[b], (unsigned long long)h);
+    }
+}
+
+// one thread per slot below its cell's count: the joint bin of (q-bar_4, q-bar_6) in the block's LDS
+// histogram, the sums of NA and the particles without a bond; one flush per block into the
+// accumulator copy of the block.  slot_in: k_boo_avg's compact array (NA4, NA6, deg, 0).
+__global__ __launch_bounds__(256) void k_boo_joint(const int16_t* __restrict__ ncnt, const int* __restrict__ slot_in,
+                                                   uint32_t slots, uint32_t nmax, int nq, int n2,
+                                                   unsigned long long* __restrict__ acc) {
+    extern __shared__ unsigned hj[];
+    const int nj = n2 * n2;
+    for (int b = threadIdx.x; b < nj; b += blockDim.x) hj[b] = 0u;
+    __syncthreads();
+    const uint32_t nthreads = gridDim.x * blockDim.x;
+    long long s4 = 0, s6 = 0, iso = 0;
+    for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < slots; id += nthreads) {
+        const uint32_t cell = id / nmax;
+        if ((int)(id - cell * nmax) >= (int)ncnt[cell]) continue;
+        const int4 v = *(const int4*)(slot_in + (size_t)id * kBooAvgSlot);
+        s4 += (long long)v.x;
+        s6 += (long long)v.y;
+        if (v.z == 0) {
+            ++iso;
+            continue;
+        }
+        const int b4 = pmc_boo_avg_bin((int64_t)v.x, v.z, 4, n2), b6 = pmc_boo_avg_bin((int64_t)v.y, v.z, 6, n2);
+        atomicAdd(&hj[b4 * n2 + b6], 1u);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s4 += __shfl_xor(s4, o);
+        s6 += __shfl_xor(s6, o);
+        iso += __shfl_xor(iso, o);
+    }
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kBooAvgCopies - 1)) * boo_avg_stride(nq, n2);
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        if (iso) atomicAdd(&mine[2], (unsigned long long)iso);
+        if (s4) atomicAdd(&mine[3], (unsigned long long)s4);
+        if (s6) atomicAdd(&mine[4], (unsigned long long)s6);
+    }
+    __syncthreads();
+    unsigned long long* gj = mine + kBooAvgHead + 2 * (size_t)nq;
+    for (int b = threadIdx.x; b < nj; b += blockDim.x) {
+        const unsigned h = hj[b];
+        if (h) atomicAdd(&gj[b], (unsigned long long)h);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // test-particle energies (include/pmc_probe.h): per owned cell, kpc Widom insertions at Philox
 // positions (PMC_PROBE_INSERT) or the cell's own particles with their own slot skipped
 // (PMC_PROBE_REAL), each against the cell's 27-cell stencil.  k_pairobs' per-cell form: the same
@@ -5814,6 +6138,44 @@ hipError_t launch_bond_order(const DevGeom& g, const float* disk, const int16_t*
     hipLaunchKernelGGL(k_cluster_flatten, grid_s, block_s, 0, st, parent, size, (uint32_t)slots);
     hipLaunchKernelGGL(k_cluster_count, grid_s, block_s, sizeof(unsigned) * (size_t)nbins, st, parent, size,
                        (uint32_t)slots, cl_acc + (size_t)kClusterCopies * (kClusterHead + kClusterDegBins), nbins);
+    return hipGetLastError();
+}
+
+// The neighbour-averaged bond order's launches (pmc_internal.h states the buffers), on launch_clusters'
+// grid for the walks: k_boo_accum with one q bin (its accumulators are not read), the normalising pass
+// and the gather walk for l = 4, the same for l = 6, then the joint histogram.  LDS per wave of the
+// gather at nmax 16 and l = 6: 10.2 KiB + 4 nq bytes; of k_boo_joint per block: 4 n2^2 bytes.
+hipError_t launch_bond_order_avg(const DevGeom& g, const float* disk, const int16_t* n, float rb2, int nq, int n2,
+                                 int* rec, int* slot, unsigned long long* boo_scratch, unsigned long long* acc,
+                                 hipStream_t st) {
+    if (nq < 1 || nq > kBooAvgMaxBins || n2 < 1 || n2 > kBooAvgMaxJoint || g.halo != 0) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells = storage cells
+    const int64_t slots = total * g.nmax;
+    if (slots >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
+    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
+    const int64_t nb = (slots + 255) / 256;
+    const dim3 grid_s((unsigned)(nb < 4096 ? nb : 4096)), block_s(256);
+    const size_t stage = 3 * 27 * (size_t)g.nmax + 32;
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
+    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
+        auto pass = [&](auto lc) {
+            constexpr int L = decltype(lc)::value;
+            const size_t lds_acc = sizeof(float) * (stage + (size_t)kWave * (2 * L + 1) + 1);
+            const size_t lds_avg = sizeof(float) * (stage + 27 * (size_t)g.nmax + (size_t)kWave * (2 * L + 1) + (size_t)nq);
+            hipLaunchKernelGGL((k_boo_accum<NS, O, L>), grid, block, lds_acc, st, g, disk, n, boo_scratch, (uint32_t)total,
+                               rb2, 1, rec);
+            hipLaunchKernelGGL(k_boo_unit, grid_s, block_s, 0, st, n, rec, (uint32_t)slots, (uint32_t)g.nmax);
+            hipLaunchKernelGGL((k_boo_avg<NS, O, L>), grid, block, lds_avg, st, g, disk, n, acc, (uint32_t)total, rb2, nq,
+                               n2, rec, slot);
+        };
+        pass(int_c<4>{});
+        pass(int_c<6>{});
+    });
+    hipLaunchKernelGGL(k_boo_joint, grid_s, block_s, sizeof(unsigned) * (size_t)n2 * (size_t)n2, st, n, slot,
+                       (uint32_t)slots, (uint32_t)g.nmax, nq, n2, acc);
     return hipGetLastError();
 }
 

@@ -7,7 +7,7 @@
  *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS] [--widom K]
  *         [--sk HMAX] [--profile AXIS[:NBINS]] [--profile-ik AXIS[:NBINS]]
  *         [--gcmc Z [--gc-moves K] [--gc-every M]] [--clusters RB[:MINNB]]
- *         [--boo L:RB[:THRESH[:MINCONN]]] [--npt P[:DW[:EVERY]] [--w-min W] [--w-max W]]
+ *         [--boo L:RB[:THRESH[:MINCONN]]] [--boo-avg RB[:NQ]] [--npt P[:DW[:EVERY]] [--w-min W] [--w-max W]]
  *
  * --dump writes create_dump frames (kernel.cu:510-536; the reference's VISUALISATION path) of the
  * initial state and after every --every sweeps; --save writes a PMCSNAP1 snapshot at the end;
@@ -56,6 +56,12 @@
  * with the sweep index, the global order parameter Q_l, the mean local <q_l>, the number of solid
  * particles, the number of solid clusters and the largest one's size, then the integers behind them;
  * at the end the final state's q_l table, one `boo_q` line per occupied bin of 100.
+ *
+ * --boo-avg RB[:NQ] runs the neighbour-averaged bond order (pmc_bond_order_avg: Lechner and Dellago's
+ * q-bar_4 and q-bar_6, bond length RB <= w, NQ histogram bins, default 100, at most 4096) with every
+ * report: one `boo_avg` line with the sweep index and the means <q-bar_4> and <q-bar_6> over the particles
+ * that have a bond, then the integers behind them; at the end the final state's two marginal tables,
+ * one `boo_qa4` / `boo_qa6` line per occupied bin.
  *
  * Prints "step: energy" lines like kernel.cu:643,695 (energy from the cell-list sum every
  * --every sweeps) and a final summary with acceptance ratio and trial-moves/s.  Compile-time
@@ -167,6 +173,34 @@ static void print_boo(pmc_ctx* ctx, unsigned step, int l, float r_bond, int c8, 
         if (h_q[b]) printf("boo_q %.3f %llu\n", ((double)b + 0.5) / NQ, (unsigned long long)h_q[b]);
 }
 
+/* --boo-avg: the report line of the current state (table 0) or its two marginal tables (table 1) */
+static void print_boo_avg(pmc_ctx* ctx, unsigned step, float r_bond, int nq, int table) {
+    enum { N2 = 50 };
+    static uint64_t h4[4096], h6[4096], hj[N2 * N2];
+    pmc_boo_avg_obs bo;
+    int rc;
+    if ((rc = pmc_bond_order_avg(ctx, r_bond, nq, N2, h4, h6, hj, NULL, &bo))) die("pmc_bond_order_avg", rc);
+    if (!table) {
+        double m4 = 0.0, m6 = 0.0;
+        uint64_t bonded = 0;
+        for (int b = 0; b < nq; ++b) {
+            m4 += ((double)b + 0.5) / nq * (double)h4[b];
+            m6 += ((double)b + 0.5) / nq * (double)h6[b];
+            bonded += h4[b];
+        }
+        printf("boo_avg %u qa4 %.9g qa6 %.9g (N %lld, bonds %lld, isolated %lld, sum NA4 %lld, sum NA6 %lld)\n", step,
+               bonded ? m4 / (double)bonded : 0.0, bonded ? m6 / (double)bonded : 0.0, (long long)bo.particles,
+               (long long)bo.bonds, (long long)bo.isolated, (long long)bo.na_sum4, (long long)bo.na_sum6);
+        return;
+    }
+    printf("# averaged local order q-bar_4, q-bar_6 (r_bond %.9g): bin centre, particles; the last bin holds "
+           "q-bar >= %.4f\n", (double)r_bond, (double)(nq - 1) / nq);
+    for (int b = 0; b < nq; ++b)
+        if (h4[b]) printf("boo_qa4 %.5f %llu\n", ((double)b + 0.5) / nq, (unsigned long long)h4[b]);
+    for (int b = 0; b < nq; ++b)
+        if (h6[b]) printf("boo_qa6 %.5f %llu\n", ((double)b + 0.5) / nq, (unsigned long long)h6[b]);
+}
+
 int main(int argc, char** argv) {
     pmc_params p;
     memset(&p, 0, sizeof(p));
@@ -179,7 +213,8 @@ int main(int argc, char** argv) {
     int npt = 0, npt_every = 1;
     float npt_p = 0.0f, npt_dw = 0.0f, w_min = 0.0f, w_max = 0.0f;
     int cl_minnb = 0, boo_l = 0, boo_c8 = 179, boo_minconn = 7;
-    float boo_rb = 0.0f;
+    float boo_rb = 0.0f, booa_rb = 0.0f;
+    int booa_nq = 100;
     const char *dump = NULL, *save = NULL, *restart = NULL;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -227,6 +262,16 @@ int main(int argc, char** argv) {
             cl_minnb = colon ? atoi(colon + 1) : 0;
             if (!(cl_rb > 0.0f) || cl_minnb < 0 || cl_minnb > 127) {
                 fprintf(stderr, "--clusters RB[:MINNB]: RB > 0, MINNB 0..127\n");
+                return 2;
+            }
+            ++i;
+        }
+        else if (!strcmp(a, "--boo-avg")) {
+            const char* c1 = strchr(v, ':');
+            booa_rb = (float)atof(v);
+            if (c1) booa_nq = atoi(c1 + 1);
+            if (!(booa_rb > 0.0f) || booa_nq < 1 || booa_nq > 4096) {
+                fprintf(stderr, "--boo-avg RB[:NQ]: RB > 0, NQ 1..4096\n");
                 return 2;
             }
             ++i;
@@ -299,6 +344,7 @@ int main(int argc, char** argv) {
     printf("0: %f\n", e);
     if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)first, cl_rb, cl_minnb, 0);
     if (boo_l) print_boo(ctx, (unsigned)first, boo_l, boo_rb, boo_c8, boo_minconn, 0);
+    if (booa_rb > 0.0f) print_boo_avg(ctx, (unsigned)first, booa_rb, booa_nq, 0);
     pmc_stats total;
     memset(&total, 0, sizeof(total));
     double seconds = 0.0;
@@ -359,6 +405,7 @@ int main(int argc, char** argv) {
         if (gcmc == 0.0f && !npt) printf("%u: %f\n", (unsigned)(s + (uint32_t)k), e);
         if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)(s + (uint32_t)k), cl_rb, cl_minnb, 0);
         if (boo_l) print_boo(ctx, (unsigned)(s + (uint32_t)k), boo_l, boo_rb, boo_c8, boo_minconn, 0);
+        if (booa_rb > 0.0f) print_boo_avg(ctx, (unsigned)(s + (uint32_t)k), booa_rb, booa_nq, 0);
         if (dump && (rc = pmc_dump_frame(ctx, dump, 1, (int64_t)(s + (uint32_t)k)))) die("pmc_dump_frame", rc);
     }
     if (save && (rc = pmc_save_snapshot(ctx, save, first + (uint32_t)passes))) die("pmc_save_snapshot", rc);
@@ -369,6 +416,7 @@ int main(int argc, char** argv) {
         printf("# device time %.6f s, %.3e trial-moves/s\n", seconds, (double)total.trials / seconds);
     if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)(first + (uint32_t)passes), cl_rb, cl_minnb, 1);
     if (boo_l) print_boo(ctx, (unsigned)(first + (uint32_t)passes), boo_l, boo_rb, boo_c8, boo_minconn, 1);
+    if (booa_rb > 0.0f) print_boo_avg(ctx, (unsigned)(first + (uint32_t)passes), booa_rb, booa_nq, 1);
     if (pairobs) {
         const double pi = 3.14159265358979323846;
         uint64_t* hist = calloc(pairobs > 0 ? (size_t)pairobs : 1, sizeof(uint64_t));

@@ -77,6 +77,12 @@ class BooObs(C.Structure):
                                          "clusters", "largest", "largest_label", "sum_s2")] + [("qsum", C.c_int64 * 13)]
 
 
+class BooAvgObs(C.Structure):
+    """``pmc_boo_avg_obs``."""
+
+    _fields_ = [(k, C.c_int64) for k in ("particles", "bonds", "isolated", "na_sum4", "na_sum6")]
+
+
 class GcStats(C.Structure):
     """``pmc_gc_stats``."""
 
@@ -138,6 +144,7 @@ PMC_SK_MAX_K, PMC_SK_MAX_H = 4096, 1024     # include/pmc_sk.h
 PMC_PROFILE_MAX_BINS, PMC_PROFILE_BINS_PER_CELL = 4096, 64     # include/pmc_profile.h
 PMC_CLUSTER_DEG_BINS, PMC_CLUSTER_MAX_BINS = 128, 4096     # include/pmc_cluster.h
 PMC_BOO_CONN_BINS, PMC_BOO_RECORD, PMC_BOO_TERMS = 128, 16, 13     # include/pmc_boo.h
+PMC_BOO_AVG_SLOT, PMC_BOO_AVG_UNIT, PMC_BOO_K4, PMC_BOO_K6 = 4, 16, 13866, 16664     # include/pmc_boo_avg.h, pmc_boo.h
 
 
 class PmcError(RuntimeError):
@@ -242,6 +249,7 @@ def lib():
         _sig(L, "pmc_clusters", i32, _vp, C.c_float, i32, i32, _vp, _vp, _vp, C.POINTER(ClusterObs))
         _sig(L, "pmc_bond_order", i32, _vp, i32, C.c_float, i32, i32, i32, i32, _vp, _vp, _vp, _vp, _vp,
              C.POINTER(BooObs))
+        _sig(L, "pmc_bond_order_avg", i32, _vp, C.c_float, i32, i32, _vp, _vp, _vp, _vp, C.POINTER(BooAvgObs))
         _sig(L, "pmc_exchange_phase", i32, _vp, i32, u32, C.c_float, i32)
         _sig(L, "pmc_exchange_sweep", i32, _vp, u32, C.c_float, i32)
         _sig(L, "pmc_gc_stats_read", i32, _vp, C.POINTER(GcStats), i32)

@@ -21,9 +21,9 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (PMC_BOO_CONN_BINS, PMC_BOO_RECORD, PMC_CLUSTER_DEG_BINS, PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT,
-                   PMC_PROBE_REAL, BooObs, ClusterObs, GcStats, NptMove, NptStats, NptSums, PairObs, Params, ProbeObs,
-                   ProfileObs, Result, SkObs, Stats, check, lib)
+from ._lib import (PMC_BOO_AVG_SLOT, PMC_BOO_CONN_BINS, PMC_BOO_RECORD, PMC_CLUSTER_DEG_BINS, PMC_IPC_HANDLE_BYTES,
+                   PMC_PROBE_INSERT, PMC_PROBE_REAL, BooAvgObs, BooObs, ClusterObs, GcStats, NptMove, NptStats, NptSums,
+                   PairObs, Params, ProbeObs, ProfileObs, Result, SkObs, Stats, check, lib)
 
 FIX_SCALE = 2.0 ** 32
 
@@ -570,6 +570,35 @@ class PmcContext:
         res.update(qsum=np.array(list(out.qsum), np.int64), q_hist=q_hist, conn_hist=conn_hist, size_hist=size_hist,
                    records=rec, labels=lab, l=int(l), r_bond=float(np.float32(r_bond)), c8=c8, threshold=c8 / 256.0,
                    min_conn=int(min_conn), nq=int(nq), nbins=int(nbins), core=int(out.solid))
+        return res
+
+    def bond_order_averaged(self, r_bond: float = 1.5, nq: int = 100, n2: int = 50, per_slot: bool = False) -> dict:
+        """Neighbour-averaged bond order of a whole-box context (pmc_bond_order_avg,
+        include/pmc_boo_avg.h): Lechner and Dellago's q-bar_4 and q-bar_6 of every particle, the norm of
+        the mean over the particle and its bonded partners (within r_bond <= w) of their normalised
+        harmonic sums.  The (q-bar_4, q-bar_6) plane separates liquid, bcc, hcp and fcc where the plain
+        q_l of bond_order overlap.  Returns qa4_hist and qa6_hist (uint64, nq bins of q-bar_l on [0, 1)),
+        joint_hist (uint64, (n2, n2): [bin of q-bar_4, bin of q-bar_6], n2 <= 64 bins per axis), the
+        integers particles, bonds, isolated (particles without a bond: in no histogram), na_sum4 and
+        na_sum6 (the exact sums of the integer norms), and r_bond, nq, n2 as used.  per_slot=True adds
+        "slots": int32 (slots, 4) in slot order, NA4, NA6, deg, 0, zeros in empty slots (q-bar_l = NA_l /
+        ((deg + 1) 16 K_l), K_4 = 13866, K_6 = 16664); otherwise "slots" is None.  Every output is exact
+        and independent of the launch shape.  observables.averaged_distribution, mean_averaged_order,
+        order_map and classify_phases convert; observables.add_bond_order_averaged accumulates samples.
+        Slab contexts are refused (the sums need the halo partners' harmonics)."""
+        slots = self.cells * self.nmax
+        qa4 = np.zeros(max(int(nq), 0), np.uint64)
+        qa6 = np.zeros(max(int(nq), 0), np.uint64)
+        joint = np.zeros((max(int(n2), 0),) * 2, np.uint64)
+        per = np.empty((slots, PMC_BOO_AVG_SLOT), np.int32) if per_slot else None
+        out = BooAvgObs()
+        check("pmc_bond_order_avg",
+              lib().pmc_bond_order_avg(self._h, r_bond, int(nq), int(n2), qa4.ctypes.data if qa4.size else None,
+                                       qa6.ctypes.data if qa6.size else None, joint.ctypes.data if joint.size else None,
+                                       per.ctypes.data if per_slot else None, C.byref(out)))
+        res = {key: int(getattr(out, key)) for key, _ in BooAvgObs._fields_}
+        res.update(qa4_hist=qa4, qa6_hist=qa6, joint_hist=joint, slots=per, r_bond=float(np.float32(r_bond)), nq=int(nq),
+                   n2=int(n2))
         return res
 
     def stats(self, reset: bool = False) -> dict:

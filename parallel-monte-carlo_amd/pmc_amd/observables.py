@@ -7,7 +7,9 @@ pressure-tensor profiles and the surface tension from the axis profiles of ``Pmc
 (pmc_profiles, include/pmc_profile.h) and ``PmcContext.profiles_ik`` (pmc_profiles_ik,
 include/pmc_profile_ik.h), and the cluster-size and coordination statistics from the integers of
 ``PmcContext.clusters`` (pmc_clusters, include/pmc_cluster.h), and the Steinhardt order-parameter
-statistics from those of ``PmcContext.bond_order`` (pmc_bond_order, include/pmc_boo.h).
+statistics from those of ``PmcContext.bond_order`` (pmc_bond_order, include/pmc_boo.h), and the
+q-bar_4 / q-bar_6 distributions, their joint map and the phase counts from those of
+``PmcContext.bond_order_averaged`` (pmc_bond_order_avg, include/pmc_boo_avg.h).
 
 Pure numpy, no GPU: the sums of several slab contexts are added first (they are exact integers),
 then converted here.  Units are the library's reduced Lennard-Jones units (epsilon = sigma_LJ = 1).
@@ -463,3 +465,81 @@ def connection_distribution(res: dict) -> tuple:
     h = np.asarray(res["conn_hist"], np.float64)
     n = float(res["particles"])
     return np.arange(len(h)), (h / n if n > 0 else h), (float(res["conn_bonds"]) / n if n > 0 else 0.0)
+
+
+# ---- neighbour-averaged bond order (PmcContext.bond_order_averaged) -----------------------------------
+_BOO_AVG_SUMS = ("particles", "bonds", "isolated", "na_sum4", "na_sum6")
+
+
+def _avg_hist(res: dict, l: int) -> np.ndarray:
+    if l not in (4, 6):
+        raise ValueError("l must be 4 or 6")
+    return np.asarray(res["qa4_hist" if l == 4 else "qa6_hist"], np.float64)
+
+
+def averaged_distribution(res: dict, l: int) -> tuple:
+    """(bin centres, p(q-bar_l)): the probability density of the neighbour-averaged order parameter
+    q-bar_l(i) = NA_l(i) / ((deg(i) + 1) 16 K_l), l = 4 or 6, over the particles that have a bond, nq bins
+    on [0, 1) (the last bin also collects q-bar_l >= 1); p integrates to 1."""
+    h = _avg_hist(res, l)
+    nq = len(h)
+    total = h.sum()
+    return (np.arange(nq) + 0.5) / nq, (h / total * nq if total > 0 else h)
+
+
+def mean_averaged_order(res: dict, l: int) -> float:
+    """<q-bar_l> over the particles that have a bond, from the histogram (bin centres: exact to 1 / (2 nq))."""
+    centres, p = averaged_distribution(res, l)
+    return float((centres * p).sum() / len(p))
+
+
+def order_map(res: dict) -> tuple:
+    """(q-bar_4 centres, q-bar_6 centres, density): the joint probability density of (q-bar_4, q-bar_6)
+    over the particles that have a bond, n2 x n2 bins on [0, 1)^2, density[bin of q-bar_4, bin of
+    q-bar_6]; it integrates to 1."""
+    h = np.asarray(res["joint_hist"], np.float64)
+    n2 = h.shape[0]
+    centres = (np.arange(n2) + 0.5) / n2
+    total = h.sum()
+    return centres, centres.copy(), (h / total * n2 * n2 if total > 0 else h)
+
+
+def classify_phases(res: dict, q6_solid: float = 0.30, q4_hcp: float = 0.06, q4_fcc: float = 0.14) -> dict:
+    """Counts of liquid, bcc, hcp and fcc particles from rectangles of the joint histogram: liquid is
+    q-bar_6 < q6_solid; of the others bcc is q-bar_4 < q4_hcp, hcp is q4_hcp <= q-bar_4 < q4_fcc and fcc
+    is q-bar_4 >= q4_fcc.  The boundaries are snapped to the nearest bin edge k / n2, and the snapped
+    values are returned as "q6_solid", "q4_hcp" and "q4_fcc"; "isolated" repeats the particles without
+    a bond, which are in no class.  The defaults sit between the perfect crystals' values (bcc 0.036,
+    hcp 0.097, fcc 0.191 in q-bar_4; all three above 0.48 in q-bar_6) and suit a cold Lennard-Jones
+    solid next to its melt; they are STATE-DEPENDENT: thermal motion lowers every crystal's q-bar_l, so
+    at another temperature or density take them from order_map's valleys.  Other structures fall in
+    the rectangle their values lie in (simple cubic, q-bar_4 = 0.76: the fcc rectangle)."""
+    h = np.asarray(res["joint_hist"], np.uint64)
+    n2 = h.shape[0]
+
+    def edge(x):
+        return min(max(int(np.floor(float(x) * n2 + 0.5)), 0), n2)
+
+    e6, e4h, e4f = edge(q6_solid), edge(q4_hcp), edge(q4_fcc)
+    if e4h > e4f:
+        raise ValueError("classify_phases: q4_hcp must not exceed q4_fcc")
+    return {"liquid": int(h[:, :e6].sum()), "bcc": int(h[:e4h, e6:].sum()), "hcp": int(h[e4h:e4f, e6:].sum()),
+            "fcc": int(h[e4f:, e6:].sum()), "isolated": int(res["isolated"]), "q6_solid": e6 / n2, "q4_hcp": e4h / n2,
+            "q4_fcc": e4f / n2}
+
+
+def add_bond_order_averaged(a: dict, b: dict) -> dict:
+    """Accumulate two averaged bond-order results (samples of one run): the histograms and the counts add
+    and "samples" counts them; the per-slot data are per sample and are dropped.  Refuses results taken
+    with a different r_bond, nq or n2."""
+    for k in ("r_bond", "nq", "n2"):
+        if a[k] != b[k]:
+            raise ValueError(f"add_bond_order_averaged: results taken with different {k}")
+    out = dict(a)
+    for k in ("qa4_hist", "qa6_hist", "joint_hist"):
+        out[k] = np.asarray(a[k], np.uint64) + np.asarray(b[k], np.uint64)
+    for k in _BOO_AVG_SUMS:
+        out[k] = int(a[k]) + int(b[k])
+    out["samples"] = int(a.get("samples", 1)) + int(b.get("samples", 1))
+    out["slots"] = None
+    return out
