@@ -119,7 +119,7 @@ def test_empty_box(oracle):
 
 
 @pytest.mark.parametrize("kw", [dict(cps=4), dict(cps=6, cps_y=4, cps_z=8, nz_local=3, z0=4, halo=1, seed=(7 << 32) | 5),
-                                dict(cps=4, w=3.1)])
+                                dict(cps=4, w=3.1), dict(cps=6, cps_y=4, cps_z=10, w=2.7)])
 def test_probe_positions(oracle, kw):
     """orc_philox and the header give the same words under the counter layout (k, gid, sample, tag 4)
     with the GLOBAL cell id; every probe lies in (lb, lb + w] of its cell up to 1 ulp."""

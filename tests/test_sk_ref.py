@@ -68,7 +68,8 @@ def _model_phase(hkl, q):
 
 @pytest.fixture(scope="module")
 def states(oracle):
-    return {"4": _evolved_state(oracle, 4, 305), "8w": _evolved_state(oracle, 8, 1500, w=3.1)}
+    return {"4": _evolved_state(oracle, 4, 305), "8w": _evolved_state(oracle, 8, 1500, w=3.1),
+            "6x4x10": _evolved_state(oracle, 6, 1001, cps_y=4, cps_z=10, w=2.7)}      # L_x and L_z round
 
 
 def test_sincos_exhaustive():
@@ -127,18 +128,20 @@ def test_halo_garbage_is_not_read(oracle):
         assert sk_ref.same(sk_ref.density_modes(ps, disk.reshape(-1), n.reshape(-1), hkl), want)
 
 
-@pytest.mark.parametrize("name", ["4", "8w"])
+@pytest.mark.parametrize("name", ["4", "8w", "6x4x10"])
 def test_exact_phase_and_true_positions(states, name):
     """re / 2^32 and im / 2^32 against float64 sums of cos / sin (a) of the exact word phase of a
     numpy model of the words, within N * TERM, and (b) of 2 pi h.r / L from the stored floats, within
     N * (TERM + 2 pi sum|h_d| 2^-24); 200 vectors including h_d = +-1024."""
     st = states[name]
-    hkl = _vectors200(11 if name == "4" else 12)
+    hkl = _vectors200({"4": 11, "8w": 12, "6x4x10": 13}[name])
     res = sk_ref.density_modes(st.p, st.disk, st.n, hkl)
     pos = st.positions()
     N = len(pos)
-    assert res["particles"] == N == (305 if name == "4" else 1500)
+    assert res["particles"] == N == {"4": 305, "8w": 1500, "6x4x10": 1001}[name]
     L = res["L"]
+    if name == "6x4x10":
+        assert [float(v) != c * float(F32(2.7)) for v, c in zip(L, (6, 4, 10))] == [True, False, True]
     q = _model_words(pos, L)
     for d in range(3):   # the model's words are the header's
         assert np.array_equal(q[:, d], sk_ref.words(pos[:, d], L[d]).astype(np.int64))
