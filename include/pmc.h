@@ -522,6 +522,28 @@ typedef struct pmc_boo_avg_obs {
 } pmc_boo_avg_obs;
 int pmc_bond_order_avg(pmc_ctx* ctx, float r_bond, int nq, int n2, uint64_t* h_qa4, uint64_t* h_qa6, uint64_t* h_joint,
                        int32_t* h_slot, pmc_boo_avg_obs* out);
+/* The pair histogram beyond the cutoff, defined bit for bit in pmc_rdf.h: the ORDERED pairs (i in an
+ * owned cell, j in the cube of (2R+1)^3 cells round it, periodic wrap) closer than r_max, for r_max up
+ * to several cell widths; R = pmc_rdf_shells(r_max, w) is the smallest number of shells that holds
+ * every such pair.  pmc_pair_observables stops at r_max <= w (one and a half peaks of g(r) at w = 2.5);
+ * this call has no virial and no cutoff in it.  The reference has no such observable.  h_hist is a HOST
+ * pointer to nbins counters: bin b counts the pairs with b * r_max / nbins <= r < (b + 1) * r_max /
+ * nbins (each unordered pair twice), with pmc_pair_observables' distance and bin arithmetic; where
+ * R = 1 the two histograms are equal bin for bin.  pmc_amd.observables.rdf_long, coordination_number
+ * and kirkwood_buff convert.
+ * PMC_ERR_ARG (outputs untouched) for a null pointer, r_max not finite or <= 0, R > 8, 2R + 1 > cps on
+ * any axis (so r_max < L / 2), nbins outside 1..4096, storage_cells * nmax >= 2^31, and for any slab
+ * context (halo != 0): a rank does not hold R planes of halo.  Runs on the context stream and
+ * synchronises; state, statistics, exchange and volume counters, error flags and the energy are left
+ * unchanged.  Device scratch (the accumulator copies, 1 MiB) is allocated on the first call and freed
+ * by pmc_destroy; a failed allocation returns PMC_ERR_HIP and leaves the context usable. */
+typedef struct pmc_rdf_obs {
+    int64_t pairs;      /* ordered pairs with r2 < r_max^2: the sum of h_hist */
+    int64_t particles;  /* particles in owned cells */
+    int32_t shells;     /* R = pmc_rdf_shells(r_max, w) */
+    int32_t pad_;
+} pmc_rdf_obs;
+int pmc_rdf_long(pmc_ctx* ctx, float r_max, int nbins, uint64_t* h_hist, pmc_rdf_obs* out);
 /* ---- grand-canonical exchange moves (mu V T) ------------------------------------------------
  * Insertions and deletions as a further kind of colour phase, defined bit for bit in pmc_gc.h: every
  * owned cell of the colour runs k_per_cell (1..64) attempts in order on its own particle list, each

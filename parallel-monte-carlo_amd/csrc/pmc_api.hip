@@ -13,6 +13,7 @@
 
 #include "pmc_ctx.h"
 #include "../../include/pmc_pairobs.h"
+#include "../../include/pmc_rdf.h"
 #include "../../include/pmc_cluster.h"
 #include "../../include/pmc_boo.h"
 #include "../../include/pmc_boo_avg.h"
@@ -26,6 +27,8 @@ using namespace pmc;
 using namespace pmc_sched;
 
 static_assert(kPairObsMaxBins == PMC_PAIROBS_MAX_BINS, "pair observables: bin cap");
+static_assert(kRdfMaxBins == PMC_RDF_MAX_BINS && kRdfMaxShells == PMC_RDF_MAX_SHELLS && sizeof(pmc_rdf_obs) == 24,
+              "multi-shell pair histogram: caps and result size");
 static_assert(kClusterMaxBins == PMC_CLUSTER_MAX_BINS && kClusterDegBins == PMC_CLUSTER_DEG_BINS, "cluster analysis: bin caps");
 static_assert(kBooMaxBins == PMC_BOO_MAX_BINS && kBooConnBins == PMC_BOO_CONN_BINS && kBooRecord == PMC_BOO_RECORD &&
                   kBooQsum + PMC_BOO_TERMS <= kBooHead && kBooOwn >= PMC_BOO_TERMS + 1,
@@ -319,6 +322,7 @@ void pmc_destroy(pmc_ctx* c) {
     if (c->eacc) (void)hipFree(c->eacc);
     if (c->segq) (void)hipFree(c->segq);
     if (c->pobs) (void)hipFree(c->pobs);
+    if (c->rdf_acc) (void)hipFree(c->rdf_acc);
     if (c->probe_acc) (void)hipFree(c->probe_acc);
     if (c->sk_acc) (void)hipFree(c->sk_acc);
     if (c->prof_acc) (void)hipFree(c->prof_acc);
@@ -717,6 +721,47 @@ int pmc_pair_observables(pmc_ctx* c, float r_max, int nbins, uint64_t* h_hist, p
     out->pairs = (int64_t)s[1];
     out->particles = (int64_t)s[2];
     for (int b = 0; b < nbins; ++b) h_hist[b] = (uint64_t)s[(size_t)kPairObsHead + (size_t)b];
+    return PMC_OK;
+}
+
+int pmc_rdf_long(pmc_ctx* c, float r_max, int nbins, uint64_t* h_hist, pmc_rdf_obs* out) {
+    if (!c || !h_hist || !out) return fail(PMC_ERR_ARG, "bad argument");
+    if (c->P.halo != 0)
+        return fail(PMC_ERR_ARG, "pmc_rdf_long: whole-box contexts only (halo == 0): a slab rank does not hold the "
+                                 "planes of halo that several shells need");
+    if (!std::isfinite(r_max) || !(r_max > 0.0f)) return fail(PMC_ERR_ARG, "pmc_rdf_long: r_max must be finite and > 0");
+    if (nbins < 1 || nbins > PMC_RDF_MAX_BINS) return fail(PMC_ERR_ARG, "pmc_rdf_long: nbins must be in 1..4096");
+    const int shells = pmc_rdf_shells(r_max, c->P.w);
+    if (shells > PMC_RDF_MAX_SHELLS) return fail(PMC_ERR_ARG, "pmc_rdf_long: r_max needs more than 8 shells of cells");
+    if (2 * shells + 1 > c->P.cps_x || 2 * shells + 1 > c->P.cps_y || 2 * shells + 1 > c->P.cps_z)
+        return fail(PMC_ERR_ARG, "pmc_rdf_long: the cube of 2 * shells + 1 cells must fit the box on every axis");
+    if (c->cells * (int64_t)c->P.nmax >= ((int64_t)1 << 31))
+        return fail(PMC_ERR_ARG, "pmc_rdf_long: storage_cells * nmax must be below 2^31");
+    if (int rj = slab_join(c)) return rj;
+    if (!c->rdf_acc) {
+        hipError_t ea = hipMalloc(&c->rdf_acc, sizeof(unsigned long long) * kRdfCopies * (kRdfHead + kRdfMaxBins));
+        if (ea != hipSuccess) {
+            c->rdf_acc = nullptr;
+            (void)hipGetLastError();   // the context stays usable
+            return hip_fail(ea, "pmc_rdf_long: scratch allocation");
+        }
+    }
+    const size_t per = (size_t)kRdfHead + (size_t)nbins;
+    PMC_HIP(hipMemsetAsync(c->rdf_acc, 0, sizeof(unsigned long long) * kRdfCopies * per, c->stream));
+    hipError_t e = launch_rdf_long(c->G, c->disk[c->cur], c->n[c->cur], c->rdf_acc, shells, pmc_pairobs_rmax2(r_max),
+                                   pmc_pairobs_bscale(r_max, nbins), nbins, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "multi-shell pair histogram launch");
+    std::vector<unsigned long long> h((size_t)kRdfCopies * per);
+    PMC_HIP(hipMemcpyAsync(h.data(), c->rdf_acc, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    std::vector<unsigned long long> s(per, 0ull);
+    for (int k = 0; k < kRdfCopies; ++k)
+        for (size_t i = 0; i < per; ++i) s[i] += h[(size_t)k * per + i];
+    out->pairs = (int64_t)s[0];
+    out->particles = (int64_t)s[1];
+    out->shells = shells;
+    out->pad_ = 0;
+    for (int b = 0; b < nbins; ++b) h_hist[b] = (uint64_t)s[(size_t)kRdfHead + (size_t)b];
     return PMC_OK;
 }
 

@@ -27,6 +27,7 @@ struct pmc_ctx {
     unsigned long long* eacc = nullptr;    // kStatSlots (energy)
     int* segq = nullptr;                   // energy: queue of row segments over the staging capacity
     unsigned long long* pobs = nullptr;    // pair observables: accumulator copies (allocated on first use)
+    unsigned long long* rdf_acc = nullptr;     // multi-shell pair histogram: accumulator copies (allocated on first use)
     unsigned long long* probe_acc = nullptr;   // test-particle energies: accumulator copies (allocated on first use)
     unsigned long long* sk_acc = nullptr;      // density modes: accumulator copies, then the vectors (grown with nk)
     int sk_cap = 0;                            // vectors sk_acc has room for

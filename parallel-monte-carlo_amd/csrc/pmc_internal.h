@@ -165,6 +165,17 @@ constexpr int kPairObsMaxBins = 512;   // PMC_PAIROBS_MAX_BINS
 static_assert((kPairObsCopies & (kPairObsCopies - 1)) == 0, "accumulator copies: a power of two");
 hipError_t launch_pairobs(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc,
                           float rmax2, float bscale, int nbins, hipStream_t st);
+// the pair histogram beyond the cutoff (k_rdf_long, pmc_rdf.h) of a whole-box context (halo == 0) with
+// 2 * shells + 1 <= cps on every axis: acc holds kRdfCopies accumulator copies of kRdfHead + nbins
+// counters each ([0] ordered pairs inside r_max, [1] owned particles, then the histogram), zeroed on st
+// before the call; the host sums the copies
+constexpr int kRdfCopies = 32;
+constexpr int kRdfHead = 2;
+constexpr int kRdfMaxBins = 4096;    // PMC_RDF_MAX_BINS
+constexpr int kRdfMaxShells = 8;     // PMC_RDF_MAX_SHELLS
+static_assert((kRdfCopies & (kRdfCopies - 1)) == 0, "accumulator copies: a power of two");
+hipError_t launch_rdf_long(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int shells,
+                           float rmax2, float bscale, int nbins, hipStream_t st);
 // volume moves (pmc_npt.h).  k_npt_sums: acc holds kNptCopies accumulator copies of the kNptHead
 // counters of pmc_npt_sums (in its order), zeroed on st before the call; the host sums the copies.
 // k_rescale: in place on a whole-box state, s = w_new / w; clamp_acc one counter, zeroed before.

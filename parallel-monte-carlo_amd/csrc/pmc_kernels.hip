@@ -26,6 +26,7 @@
 #include "pmc_internal.h"
 #include "../../include/pmc_detmath.h"
 #include "../../include/pmc_pairobs.h"
+#include "../../include/pmc_rdf.h"
 #include "../../include/pmc_cluster.h"
 #include "../../include/pmc_boo.h"
 #include "../../include/pmc_boo_avg.h"
@@ -5179,6 +5180,165 @@ __global__ __launch_bounds__(kWave) void k_sk(DevGeom g, const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------
+// the pair histogram beyond the cutoff (include/pmc_rdf.h): ORDERED pairs (i in an owned cell, j in the
+// cube of (2R+1)^3 cells round it) closer than r_max, binned with pmc_pairobs.h's arithmetic.  No
+// stencil table and no staging filter: the cube has up to 17^3 cells and most partners are wanted.
+// One wavefront per run of kRdfRun owned cells (launch_pairobs' fixed grid).  Per own cell: its
+// particles sit in registers, lane i = slot i (nmax <= 64), and are broadcast by readlane.  The cube is
+// walked in blocks of 64 cells, one cell per lane: offset, far test (pmc_rdf_cell_far: the corners of
+// the cube, 30 % of its cells at eight shells, hold nothing inside r_max), periodic wrap with its image shift, the
+// count.  A wave scan of the counts turns the block into a dense partner list -- every lane writes one
+// 16-bit descriptor (source lane, slot) per particle of its cell into LDS -- so the 64 partner lanes of
+// a pass are full whatever the cells hold (4.8 particles on average, many empty cells at low density).
+// A partner lane reads its descriptor, fetches the cell index and the shift from the source lane,
+// loads the slot through DiskAddr and adds the shift; only slots below the count are ever addressed.
+// Then every own particle against the 64 partners: r2, compare, and for the pairs inside r_max sqrt,
+// scale, convert and a returnless ds_add_u32 into the wave's private LDS histogram.
+// u32 bins cannot wrap: `since` bounds the pairs binned since the last flush by the distances
+// evaluated, a cell adds at most nmax^2 (2R+1)^3 <= 64^2 17^3 = 2.0e7 of them, and the wave flushes
+// after the cell that takes `since` to 2^31: no bin exceeds 2^31 + 2.0e7 < 2^32, even with nbins = 1.
+// Flush: the nonzero bins by 64-bit global atomics into one of kRdfCopies accumulator copies
+// ([pairs, particles, hist[nbins]] each) the host sums.  Integer sums only, equal to tests/rdf_ref.c.
+// ------------------------------------------------------------------------------------------
+constexpr int kRdfRun = 8;      // consecutive cells per wave and stride step
+
+template <bool OFF32>
+__global__ __launch_bounds__(kWave) void k_rdf_long(DevGeom g, const float* __restrict__ disk,
+                                                    const int16_t* __restrict__ ncnt,
+                                                    unsigned long long* __restrict__ acc, uint32_t total_cells, int R,
+                                                    UDivMagic div_n1, UDivMagic div_n2, float rmax2, float bscale,
+                                                    int nbins) {
+    extern __shared__ __attribute__((aligned(16))) float psm[];
+    using DA = DiskAddr<OFF32>;
+    unsigned* hist = (unsigned*)psm;                       // nbins counters of this wave
+    uint16_t* desc = (uint16_t*)(hist + nbins);            // partner list of a cube block: 64 * nmax entries
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int n1 = 2 * R + 1;
+    const int ncube = n1 * n1 * n1;
+    const int centre = (ncube - 1) / 2;                    // offset (0, 0, 0): the own cell, handled apart
+    unsigned long long n_pairs = 0, n_part = 0, since = 0; // wave-uniform
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kRdfCopies - 1)) * (size_t)(kRdfHead + nbins);
+    for (int b = lane; b < nbins; b += kWave) hist[b] = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+
+    auto flush = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        for (int b = lane; b < nbins; b += kWave) {
+            const unsigned h = hist[b];
+            if (h) {
+                atomicAdd(&mine[kRdfHead + b], (unsigned long long)h);
+                hist[b] = 0u;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        since = 0;
+    };
+
+    const uint32_t stride = gridDim.x * (uint32_t)kRdfRun;
+    for (uint32_t base = blockIdx.x * (uint32_t)kRdfRun; base < total_cells; base += stride) {
+        const int ncl = (int)(total_cells - base < (uint32_t)kRdfRun ? total_cells - base : (uint32_t)kRdfRun);
+        for (int c = 0; c < ncl; ++c) {
+            const uint32_t t = base + (uint32_t)c;         // whole box: storage cell = owned cell
+            int n_own = wave_uniform((int)ncnt[t]);
+            n_own = n_own < 0 ? 0 : (n_own > nm ? nm : n_own);
+            n_part += (unsigned long long)n_own;
+            if (n_own == 0) continue;
+            const uint32_t q1 = udiv_magic(t, g.div_cx);
+            const uint32_t zq = udiv_magic(t, g.div_plane);
+            const int x = (int)(t - q1 * (uint32_t)g.cps_x);
+            const int y = (int)(q1 - zq * (uint32_t)g.cps_y);
+            const int z = (int)zq;
+            float ox = 0.0f, oy = 0.0f, oz = 0.0f;         // own particle `lane`
+            if (lane < n_own) {
+                const uint32_t off = (t * (uint32_t)(3 * nm) + (uint32_t)lane * lay_slot()) * DA::kUnit;
+                DA::ld3(disk, off, lay_dim(nm), ox, oy, oz);
+            }
+            // every own particle i against the 64 partner lanes (vm: the lanes that hold one); in the own
+            // cell's block the term j == i is skipped
+            auto block = [&](float xj, float yj, float zj, unsigned long long vm, auto own_c) {
+                constexpr bool kOwn = decltype(own_c)::value;
+                for (int i = 0; i < n_own; ++i) {
+                    const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+                    const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+                    const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+                    const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
+                    unsigned long long im = __builtin_amdgcn_ballot_w64(r2 < rmax2) & vm;
+                    if constexpr (kOwn) im &= ~(1ull << i);
+                    if (__builtin_amdgcn_inverse_ballot_w64(im))
+                        (void)__hip_atomic_fetch_add(&hist[pmc_pairobs_bin(r2, bscale, nbins)], 1u, __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_WORKGROUP);
+                    n_pairs += (unsigned long long)__popcll(im);
+                }
+            };
+            block(ox, oy, oz, __builtin_amdgcn_ballot_w64(lane < n_own), std::true_type{});
+            since += (unsigned long long)n_own * (unsigned long long)n_own;
+
+            for (int cb = 0; cb < ncube; cb += kWave) {
+                // ---- one cube cell per lane
+                const int e = cb + lane;
+                const bool live = e < ncube && e != centre;
+                const uint32_t ee = (uint32_t)(live ? e : centre);
+                const uint32_t u2 = udiv_magic(ee, div_n2);                   // ee / n1^2
+                const uint32_t rem = ee - u2 * (uint32_t)(n1 * n1);
+                const uint32_t u1 = udiv_magic(rem, div_n1);                  // rem / n1
+                const int dx = (int)(rem - u1 * (uint32_t)n1) - R, dy = (int)u1 - R, dz = (int)u2 - R;
+                const int nx0 = x + dx, ny0 = y + dy, nz0 = z + dz;           // 2R + 1 <= cps: one wrap at most
+                const int nx = nx0 + (nx0 < 0 ? g.cps_x : 0) - (nx0 >= g.cps_x ? g.cps_x : 0);
+                const int ny = ny0 + (ny0 < 0 ? g.cps_y : 0) - (ny0 >= g.cps_y ? g.cps_y : 0);
+                const int nz = nz0 + (nz0 < 0 ? g.cps_z : 0) - (nz0 >= g.cps_z ? g.cps_z : 0);
+                const float sx = nx0 < 0 ? -g.Lx : (nx0 >= g.cps_x ? g.Lx : 0.0f);
+                const float sy = ny0 < 0 ? -g.Ly : (ny0 >= g.cps_y ? g.Ly : 0.0f);
+                const float sz = nz0 < 0 ? -g.Lz : (nz0 >= g.cps_z ? g.Lz : 0.0f);
+                const int kc = nx + g.cps_x * (ny + g.cps_y * nz);
+                int cnt = 0;
+                if (live && !pmc_rdf_cell_far(dx, dy, dz, g.w, rmax2)) {
+                    cnt = (int)ncnt[kc];
+                    cnt = cnt < 0 ? 0 : (cnt > nm ? nm : cnt);
+                }
+                // ---- dense partner list: inclusive scan of the counts, one descriptor per particle
+                int inc = cnt;
+#pragma unroll
+                for (int o = 1; o < kWave; o <<= 1) {
+                    const int up = __shfl_up(inc, o);
+                    inc += lane >= o ? up : 0;
+                }
+                const int T = __builtin_amdgcn_readlane(inc, kWave - 1);      // partners of the block, <= 64 * nmax
+                if (T == 0) continue;
+                const int first = inc - cnt;
+                for (int s = 0; __builtin_amdgcn_ballot_w64(s < cnt) != 0ull; ++s)
+                    if (s < cnt) desc[first + s] = (uint16_t)(lane | (s << 6));
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                since += (unsigned long long)n_own * (unsigned long long)T;
+                // ---- 64 partners per pass
+                for (int pb = 0; pb < T; pb += kWave) {
+                    const int p = pb + lane;
+                    const bool vj = p < T;
+                    const int d = vj ? (int)desc[p] : 0;
+                    const int src = d & (kWave - 1), slot = d >> 6;
+                    const int c_idx = __shfl(kc, src);
+                    const float isx = __shfl(sx, src), isy = __shfl(sy, src), isz = __shfl(sz, src);
+                    float xj = 0.0f, yj = 0.0f, zj = 0.0f;
+                    if (vj) {
+                        const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)slot * lay_slot()) * DA::kUnit;
+                        DA::ld3(disk, off, lay_dim(nm), xj, yj, zj);
+                        xj = xj + isx;   // (+0 for the cells that are not wrapped)
+                        yj = yj + isy;
+                        zj = zj + isz;
+                    }
+                    block(xj, yj, zj, __builtin_amdgcn_ballot_w64(vj), std::false_type{});
+                }
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");       // the next block rewrites desc
+            }
+            if (since >= (1ull << 31)) flush();
+        }
+    }
+    flush();
+    const unsigned long long head2 = lane == 0 ? n_pairs : n_part;
+    if (lane < kRdfHead && head2 != 0) atomicAdd(&mine[lane], head2);
+}
+
+// ------------------------------------------------------------------------------------------
 // self-test of the deterministic math on the device (compared bitwise with the host oracle)
 // ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
@@ -6025,6 +6185,31 @@ hipError_t launch_pairobs(const DevGeom& g, const float* disk, const int16_t* n,
         constexpr bool O = decltype(off)::value;
         hipLaunchKernelGGL((k_pairobs<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, rmax2, bscale,
                            nbins);
+    });
+    return hipGetLastError();
+}
+
+// acc: kRdfCopies copies of [pairs, particles, hist[nbins]], zeroed on st before the call.  A fixed grid
+// like launch_pairobs', of at most 8192 waves (8 per SIMD of the chip).  LDS per wave: 4 nbins bytes
+// of histogram and 128 nmax bytes of partner list -- 3 KiB at 256 bins and nmax 16 (the wave slots, not
+// the LDS, bound the occupancy), 18 KiB at 4096 bins (8 waves per CU).  The geometry checks are the
+// kernel's bounds: halo == 0 (storage cell = owned cell) and 2 shells + 1 <= cps (one wrap per axis).
+hipError_t launch_rdf_long(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc, int shells,
+                           float rmax2, float bscale, int nbins, hipStream_t st) {
+    if (nbins < 1 || nbins > kRdfMaxBins || shells < 1 || shells > kRdfMaxShells || g.halo != 0 || g.nmax > kWave)
+        return hipErrorInvalidValue;
+    const int n1 = 2 * shells + 1;
+    if (n1 > g.cps_x || n1 > g.cps_y || n1 > g.cps_z || g.nz_local != g.cps_z) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
+    const int64_t runs = (total + kRdfRun - 1) / kRdfRun;
+    const dim3 grid((unsigned)(runs < 8192 ? runs : 8192)), block(kWave);
+    const size_t lds = sizeof(unsigned) * (size_t)nbins + sizeof(uint16_t) * (size_t)kWave * (size_t)g.nmax;
+    const UDivMagic d1 = make_udiv_magic((uint32_t)n1), d2 = make_udiv_magic((uint32_t)(n1 * n1));
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
+    with_bool(!force64 && disk_off32(g), [&](auto off) {
+        constexpr bool O = decltype(off)::value;
+        hipLaunchKernelGGL((k_rdf_long<O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, shells, d1, d2, rmax2,
+                           bscale, nbins);
     });
     return hipGetLastError();
 }

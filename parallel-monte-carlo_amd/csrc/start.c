@@ -8,6 +8,7 @@
  *         [--sk HMAX] [--profile AXIS[:NBINS]] [--profile-ik AXIS[:NBINS]]
  *         [--gcmc Z [--gc-moves K] [--gc-every M]] [--clusters RB[:MINNB]]
  *         [--boo L:RB[:THRESH[:MINCONN]]] [--boo-avg RB[:NQ]] [--npt P[:DW[:EVERY]] [--w-min W] [--w-max W]]
+ *         [--rdf RMAX[:NBINS]]
  *
  * --dump writes create_dump frames (kernel.cu:510-536; the reference's VISUALISATION path) of the
  * initial state and after every --every sweeps; --save writes a PMCSNAP1 snapshot at the end;
@@ -62,6 +63,14 @@
  * report: one `boo_avg` line with the sweep index and the means <q-bar_4> and <q-bar_6> over the particles
  * that have a bond, then the integers behind them; at the end the final state's two marginal tables,
  * one `boo_qa4` / `boo_qa6` line per occupied bin.
+ *
+ * --rdf RMAX[:NBINS] samples the pair histogram beyond the cutoff (pmc_rdf_long: RMAX up to several cell
+ * widths, below half the shortest box length; NBINS defaults to 256, at most 4096) with every report after
+ * the first (the starting state, a lattice unless --restart is given, would put its delta peaks into the
+ * average) and accumulates: one `rdf` line with the sweep index, the sample's ordered pairs inside RMAX, N and the
+ * number of cell shells walked; at the end the table over all samples, one `rdf_g` line per bin with the
+ * bin centre, g(r) and the running coordination number N(r) at the bin's upper edge.  Not with --npt (the
+ * box changes between samples).
  *
  * Prints "step: energy" lines like kernel.cu:643,695 (energy from the cell-list sum every
  * --every sweeps) and a final summary with acceptance ratio and trial-moves/s.  Compile-time
@@ -201,6 +210,38 @@ static void print_boo_avg(pmc_ctx* ctx, unsigned step, float r_bond, int nq, int
         if (h6[b]) printf("boo_qa6 %.5f %llu\n", ((double)b + 0.5) / nq, (unsigned long long)h6[b]);
 }
 
+/* --rdf: sample the current state into the run's sums and print its report line (table 0), or print the
+ * table of the sums (table 1) */
+static void print_rdf(pmc_ctx* ctx, unsigned step, float r_max, int nbins, int table) {
+    static uint64_t hist[4096], sum[4096];
+    static long long samples, particles;
+    int rc;
+    if (!table) {
+        pmc_rdf_obs ro;
+        if ((rc = pmc_rdf_long(ctx, r_max, nbins, hist, &ro))) die("pmc_rdf_long", rc);
+        for (int b = 0; b < nbins; ++b) sum[b] += hist[b];
+        ++samples;
+        particles += (long long)ro.particles;
+        printf("rdf %u pairs %lld (N %lld, shells %d)\n", step, (long long)ro.pairs, (long long)ro.particles, (int)ro.shells);
+        return;
+    }
+    const double pi = 3.14159265358979323846;
+    pmc_params q;
+    if ((rc = pmc_get_params(ctx, &q))) die("pmc_get_params", rc);
+    const double vol = (double)((float)q.cps_x * q.w) * (double)((float)q.cps_y * q.w) * (double)((float)q.cps_z * q.w);
+    const double n = samples ? (double)particles / (double)samples : 0.0, rho = n / vol, dr = (double)r_max / nbins;
+    double cum = 0.0;
+    printf("# g(r) to r_max %.9g over %lld samples (mean N %.3f): bin centre, g, N(r) at the bin's upper edge\n",
+           (double)r_max, samples, n);
+    for (int b = 0; b < nbins; ++b) {
+        const double r0 = b * dr, r1 = (b + 1) * dr;
+        const double shell = 4.0 / 3.0 * pi * (r1 * r1 * r1 - r0 * r0 * r0);
+        cum += (double)sum[b];
+        printf("rdf_g %.6f %.6f %.6f\n", 0.5 * (r0 + r1), n > 0 ? (double)sum[b] / ((double)samples * n * rho * shell) : 0.0,
+               particles ? cum / (double)particles : 0.0);
+    }
+}
+
 int main(int argc, char** argv) {
     pmc_params p;
     memset(&p, 0, sizeof(p));
@@ -214,7 +255,8 @@ int main(int argc, char** argv) {
     float npt_p = 0.0f, npt_dw = 0.0f, w_min = 0.0f, w_max = 0.0f;
     int cl_minnb = 0, boo_l = 0, boo_c8 = 179, boo_minconn = 7;
     float boo_rb = 0.0f, booa_rb = 0.0f;
-    int booa_nq = 100;
+    int booa_nq = 100, rdf_bins = 256;
+    float rdf_rmax = 0.0f;
     const char *dump = NULL, *save = NULL, *restart = NULL;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -276,6 +318,16 @@ int main(int argc, char** argv) {
             }
             ++i;
         }
+        else if (!strcmp(a, "--rdf")) {
+            const char* c1 = strchr(v, ':');
+            rdf_rmax = (float)atof(v);
+            if (c1) rdf_bins = atoi(c1 + 1);
+            if (!(rdf_rmax > 0.0f) || rdf_bins < 1 || rdf_bins > 4096) {
+                fprintf(stderr, "--rdf RMAX[:NBINS]: RMAX > 0, NBINS 1..4096\n");
+                return 2;
+            }
+            ++i;
+        }
         else if (!strcmp(a, "--boo")) {
             const char* c1 = strchr(v, ':');
             const char* c2 = c1 ? strchr(c1 + 1, ':') : NULL;
@@ -315,6 +367,7 @@ int main(int argc, char** argv) {
     if (sk < 0 || sk > 1024) { fprintf(stderr, "--sk HMAX: 1..1024\n"); return 2; }
     if (gcmc != 0.0f && graph) { fprintf(stderr, "--gcmc cannot be combined with --graph\n"); return 2; }
     if (npt && (graph || gcmc != 0.0f)) { fprintf(stderr, "--npt cannot be combined with --graph or --gcmc\n"); return 2; }
+    if (npt && rdf_rmax > 0.0f) { fprintf(stderr, "--rdf cannot be combined with --npt (the box changes between samples)\n"); return 2; }
 
     pmc_ctx* ctx = NULL;
     int rc;
@@ -406,6 +459,7 @@ int main(int argc, char** argv) {
         if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)(s + (uint32_t)k), cl_rb, cl_minnb, 0);
         if (boo_l) print_boo(ctx, (unsigned)(s + (uint32_t)k), boo_l, boo_rb, boo_c8, boo_minconn, 0);
         if (booa_rb > 0.0f) print_boo_avg(ctx, (unsigned)(s + (uint32_t)k), booa_rb, booa_nq, 0);
+        if (rdf_rmax > 0.0f) print_rdf(ctx, (unsigned)(s + (uint32_t)k), rdf_rmax, rdf_bins, 0);
         if (dump && (rc = pmc_dump_frame(ctx, dump, 1, (int64_t)(s + (uint32_t)k)))) die("pmc_dump_frame", rc);
     }
     if (save && (rc = pmc_save_snapshot(ctx, save, first + (uint32_t)passes))) die("pmc_save_snapshot", rc);
@@ -417,6 +471,7 @@ int main(int argc, char** argv) {
     if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)(first + (uint32_t)passes), cl_rb, cl_minnb, 1);
     if (boo_l) print_boo(ctx, (unsigned)(first + (uint32_t)passes), boo_l, boo_rb, boo_c8, boo_minconn, 1);
     if (booa_rb > 0.0f) print_boo_avg(ctx, (unsigned)(first + (uint32_t)passes), booa_rb, booa_nq, 1);
+    if (rdf_rmax > 0.0f) print_rdf(ctx, (unsigned)(first + (uint32_t)passes), rdf_rmax, rdf_bins, 1);
     if (pairobs) {
         const double pi = 3.14159265358979323846;
         uint64_t* hist = calloc(pairobs > 0 ? (size_t)pairobs : 1, sizeof(uint64_t));

@@ -44,6 +44,12 @@ class PairObs(C.Structure):
     _fields_ = [("virial_fixed", C.c_int64), ("pairs", C.c_int64), ("particles", C.c_int64)]
 
 
+class RdfObs(C.Structure):
+    """``pmc_rdf_obs``."""
+
+    _fields_ = [("pairs", C.c_int64), ("particles", C.c_int64), ("shells", C.c_int32), ("pad_", C.c_int32)]
+
+
 class ProbeObs(C.Structure):
     """``pmc_probe_obs``."""
 
@@ -140,6 +146,7 @@ PMC_OK, PMC_ERR_ARG, PMC_ERR_HIP, PMC_ERR_OVERFLOW, PMC_ERR_RANGE, PMC_ERR_NODEV
 PMC_IPC_HANDLE_BYTES = 1024     # include/pmc.h
 PMC_LAYOUT_REFERENCE, PMC_LAYOUT_PACKED = 0, 1
 PMC_PROBE_INSERT, PMC_PROBE_REAL = 0, 1     # include/pmc_probe.h
+PMC_RDF_MAX_SHELLS, PMC_RDF_MAX_BINS = 8, 4096     # include/pmc_rdf.h
 PMC_SK_MAX_K, PMC_SK_MAX_H = 4096, 1024     # include/pmc_sk.h
 PMC_PROFILE_MAX_BINS, PMC_PROFILE_BINS_PER_CELL = 4096, 64     # include/pmc_profile.h
 PMC_CLUSTER_DEG_BINS, PMC_CLUSTER_MAX_BINS = 128, 4096     # include/pmc_cluster.h
@@ -241,6 +248,7 @@ def lib():
              C.POINTER(C.c_int), C.POINTER(C.c_float))
         _sig(L, "pmc_energy", i32, _vp, C.POINTER(C.c_double))
         _sig(L, "pmc_pair_observables", i32, _vp, C.c_float, i32, _vp, C.POINTER(PairObs))
+        _sig(L, "pmc_rdf_long", i32, _vp, C.c_float, i32, _vp, C.POINTER(RdfObs))
         _sig(L, "pmc_probe_energies", i32, _vp, i32, i32, u32, C.c_float, C.c_float, i32, _vp, _vp,
              C.POINTER(ProbeObs))
         _sig(L, "pmc_density_modes", i32, _vp, _vp, i32, _vp, _vp, C.POINTER(SkObs))

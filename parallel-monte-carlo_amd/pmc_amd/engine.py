@@ -23,7 +23,7 @@ import numpy as np
 
 from ._lib import (PMC_BOO_AVG_SLOT, PMC_BOO_CONN_BINS, PMC_BOO_RECORD, PMC_CLUSTER_DEG_BINS, PMC_IPC_HANDLE_BYTES,
                    PMC_PROBE_INSERT, PMC_PROBE_REAL, BooAvgObs, BooObs, ClusterObs, GcStats, NptMove, NptStats, NptSums,
-                   PairObs, Params, ProbeObs, ProfileObs, Result, SkObs, Stats, check, lib)
+                   PairObs, Params, ProbeObs, ProfileObs, RdfObs, Result, SkObs, Stats, check, lib)
 
 FIX_SCALE = 2.0 ** 32
 
@@ -399,6 +399,26 @@ class PmcContext:
                                          hist.ctypes.data if hist.size else None, C.byref(out)))
         return {"hist": hist, "virial_fixed": int(out.virial_fixed), "pairs": int(out.pairs),
                 "particles": int(out.particles)}
+
+    def rdf_long(self, r_max: float, nbins: int = 256) -> dict:
+        """The pair histogram beyond the cutoff of a whole-box context (pmc_rdf_long, include/pmc_rdf.h):
+        the ordered pairs closer than r_max, for r_max up to several cell widths -- the shells of g(r) that
+        pair_observables (r_max <= w) cannot see.  The walk covers the cube of (2 shells + 1)^3 cells round
+        every cell; shells is the smallest count that holds every pair (at most 8, and 2 shells + 1 <= cps
+        on every axis, so r_max < L / 2).  Returns hist (uint64, nbins <= 4096 bins of width r_max / nbins),
+        pairs (its sum), particles, shells, r_max (the float32 value as used) and the box lengths L
+        (float64).  Where shells == 1 the histogram equals pair_observables' bin for bin.  Every output is
+        exact and independent of the launch shape.  observables.add_rdf accumulates samples;
+        observables.rdf_long, coordination_number and kirkwood_buff convert.  Slab contexts are refused
+        (a rank does not hold the planes of halo)."""
+        hist = np.zeros(max(int(nbins), 0), np.uint64)
+        out = RdfObs()
+        check("pmc_rdf_long",
+              lib().pmc_rdf_long(self._h, r_max, int(nbins), hist.ctypes.data if hist.size else None, C.byref(out)))
+        w = np.float32(self.w)
+        L = np.array([np.float32(self.cps_x) * w, np.float32(self.cps_y) * w, np.float32(self.cps_z) * w], np.float64)
+        return {"hist": hist, "pairs": int(out.pairs), "particles": int(out.particles), "shells": int(out.shells),
+                "r_max": float(np.float32(r_max)), "L": L}
 
     def probe_energies(self, mode="insert", k: int = 1, sample: int = 0, e_lo: float = -32.0, e_hi: float = 96.0,
                        nbins: int = 512) -> dict:

@@ -9,7 +9,9 @@ include/pmc_profile_ik.h), and the cluster-size and coordination statistics from
 ``PmcContext.clusters`` (pmc_clusters, include/pmc_cluster.h), and the Steinhardt order-parameter
 statistics from those of ``PmcContext.bond_order`` (pmc_bond_order, include/pmc_boo.h), and the
 q-bar_4 / q-bar_6 distributions, their joint map and the phase counts from those of
-``PmcContext.bond_order_averaged`` (pmc_bond_order_avg, include/pmc_boo_avg.h).
+``PmcContext.bond_order_averaged`` (pmc_bond_order_avg, include/pmc_boo_avg.h), and g(r) over several
+shells, the running coordination number and the Kirkwood-Buff integral from the pair histogram of
+``PmcContext.rdf_long`` (pmc_rdf_long, include/pmc_rdf.h).
 
 Pure numpy, no GPU: the sums of several slab contexts are added first (they are exact integers),
 then converted here.  Units are the library's reduced Lennard-Jones units (epsilon = sigma_LJ = 1).
@@ -543,3 +545,62 @@ def add_bond_order_averaged(a: dict, b: dict) -> dict:
     out["samples"] = int(a.get("samples", 1)) + int(b.get("samples", 1))
     out["slots"] = None
     return out
+
+
+# ---- g(r) beyond the cutoff (PmcContext.rdf_long, include/pmc_rdf.h) ----------------------------
+
+def add_rdf(a: dict, b: dict) -> dict:
+    """Accumulate two multi-shell pair histograms (samples of one run): hist, pairs and particles add and
+    "samples" counts them.  Refuses results taken with a different r_max, number of bins or box (L): an
+    NPT run changes L between samples, and its histograms over different boxes do not add."""
+    if a["r_max"] != b["r_max"]:
+        raise ValueError("add_rdf: results taken with different r_max")
+    if len(a["hist"]) != len(b["hist"]):
+        raise ValueError("add_rdf: results taken with different nbins")
+    if not np.array_equal(np.asarray(a["L"], np.float64), np.asarray(b["L"], np.float64)):
+        raise ValueError("add_rdf: results taken in different boxes (L)")
+    out = dict(a)
+    out["hist"] = np.asarray(a["hist"], np.uint64) + np.asarray(b["hist"], np.uint64)
+    for k in ("pairs", "particles"):
+        out[k] = int(a[k]) + int(b[k])
+    out["samples"] = int(a.get("samples", 1)) + int(b.get("samples", 1))
+    return out
+
+
+def _rdf_geometry(res: dict) -> tuple:
+    """(upper bin edges, mean particle number, volume, samples) of an rdf_long result or an add_rdf sum."""
+    samples = int(res.get("samples", 1))
+    nb = len(res["hist"])
+    edges = np.linspace(0.0, float(res["r_max"]), nb + 1)[1:]
+    volume = float(np.prod(np.asarray(res["L"], np.float64)))
+    return edges, res["particles"] / samples, volume, samples
+
+
+def rdf_long(res: dict) -> tuple:
+    """(bin centres, g) of an rdf_long result or an add_rdf sum: the histogram per sample over the
+    ideal-gas shell count N rho 4/3 pi (r_{b+1}^3 - r_b^3), N = particles / samples, rho = N / V with V
+    the product of L (``rdf`` on the per-sample histogram)."""
+    _, n, volume, samples = _rdf_geometry(res)
+    return rdf(np.asarray(res["hist"], np.float64) / samples, n, volume, res["r_max"])
+
+
+def coordination_number(res: dict) -> tuple:
+    """(upper bin edges, N(r)): the running coordination number, the cumulative histogram over the
+    particles -- the mean number of partners closer than r, exact from the counts."""
+    edges, _, _, _ = _rdf_geometry(res)
+    return edges, np.cumsum(np.asarray(res["hist"], np.float64)) / float(res["particles"])
+
+
+def kirkwood_buff(res: dict) -> tuple:
+    """(upper bin edges, G(r)): the running Kirkwood-Buff integral G(R) = 4 pi int_0^R (g - 1) r^2 dr =
+    (N(R) - rho 4/3 pi R^3) / rho, exact from the counts (no quadrature of g).
+
+    At fixed N (every run but run_gc) a particle has exactly N - 1 partners in the box, so g tends to
+    1 - 1/N and G(R) tends to -1/rho as the sphere fills the box, NOT to the compressibility integral
+    rho kT kappa_T - 1 / rho; read the plateau at R well below L / 2 and correct for the 1/N offset (or
+    extrapolate in 1/L).  Grand-canonical runs (``run_gc``) do not have this offset: there the plateau is
+    the compressibility integral."""
+    edges, n, volume, _ = _rdf_geometry(res)
+    rho = n / volume
+    _, nr = coordination_number(res)
+    return edges, (nr - rho * 4.0 / 3.0 * np.pi * edges ** 3) / rho
