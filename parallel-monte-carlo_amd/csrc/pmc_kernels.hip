@@ -2567,16 +2567,273 @@ __device__ __forceinline__ PairObsStencil pairobs_stencil(const DevGeom& g, cons
     return e;
 }
 
+// ------------------------------------------------------------------------------------------
+// the cell walk (DESIGN "the cell walk"): the one copy of the per-cell form above, shared by every
+// observable that visits the directed 27-cell shell.  A wave owns one CellWalk.  Per cell it stages
+// the own cell's particles first, in slot order and unfiltered (staged entry i < n_own IS own slot
+// i), then those of stencil cells 1..26 that pass pmc_box_d2 <= rc2f against the cell's box, into
+// ex/ey/ez (capacity 27 * nmax each); no slot at or past its cell's count is read.  run() strides a
+// fixed grid of waves over runs of kPairObsRun cells and issues the next cell's rows before the
+// body runs, so their loads are in flight under it.
+//
+// Payload: one more word per particle, staged beside the position in ep (27 * nmax words).
+//   NoPayload            nothing loaded, stored or reserved
+//   TagPayload<ON, F>    int f(storage cell, slot), -1 on the lanes without a particle; ON = false is
+//                        NoPayload (for a kernel that tags in one of its instantiations only)
+//   WordPayload<F>       uint32_t f(x, y, z) of the STORED coordinates (before the image shift), 0
+//                        on the lanes without a particle
+// ------------------------------------------------------------------------------------------
+struct NoPayload {
+    using T = int;
+    static constexpr bool kStaged = false, kOfPosition = false;
+    __device__ __forceinline__ T none() const { return 0; }
+    __device__ __forceinline__ T operator()(int, int) const { return 0; }
+};
+template <bool ON, class F>
+struct TagPayload {
+    using T = int;
+    static constexpr bool kStaged = ON, kOfPosition = false;
+    F f;
+    __device__ __forceinline__ T none() const { return -1; }
+    __device__ __forceinline__ T operator()(int cell, int slot) const {
+        if constexpr (ON) return f(cell, slot);
+        else return -1;
+    }
+};
+template <bool ON = true, class F>
+__device__ __forceinline__ TagPayload<ON, F> tag_payload(F f) { return TagPayload<ON, F>{f}; }
+template <class F>
+struct WordPayload {
+    using T = uint32_t;
+    static constexpr bool kStaged = true, kOfPosition = true;
+    F f;
+    __device__ __forceinline__ T none() const { return 0u; }
+    __device__ __forceinline__ T operator()(float x, float y, float z) const { return f(x, y, z); }
+};
+template <class F>
+__device__ __forceinline__ WordPayload<F> word_payload(F f) { return WordPayload<F>{f}; }
+
+// the cell a body works on (wave-uniform): its coordinates (zg global) and its storage index
+struct WalkCell {
+    int x, y, zg, kc;
+};
+
+template <int NSLOT, bool OFF32, class Pay = NoPayload>
+struct CellWalk {
+    static constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
+    static constexpr int CPP = kWave / HS;    // cells per staging pass
+    static constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
+    using DA = DiskAddr<OFF32>;
+    using PT = typename Pay::T;
+    const DevGeom& g;
+    const float* disk;
+    const int16_t* ncnt;
+    float *ex, *ey, *ez;   // staged positions, image-shifted
+    PT* ep;                // staged payload (Pay::kStaged)
+    int* inv_l;            // list entry -> stencil lane (32 ints)
+    const Pay pay;
+    const int lane, nm, p, ee;
+    // rows of the cell in flight: slots [0, HS) of its occupied stencil cells (own cell: entry 0 when
+    // occupied), in registers
+    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
+    PT vp[NPMAX];
+    bool vact[NPMAX];
+    int ncells = 0;
+    PairObsStencil cur, nxt;   // the cell being staged, the one after it
+    int S = 0;                 // staged particles
+
+    // stage: 3 * 27 * nmax floats; tags: 27 * nmax words (unused without a staged payload); list: 32
+    // ints.  Zeroes the list and fences: the caller's own LDS initialisation goes before it.
+    __device__ __forceinline__ CellWalk(const DevGeom& g_, const float* disk_, const int16_t* ncnt_, float* stage,
+                                        PT* tags, int* list, Pay pay_ = Pay{})
+        : g(g_), disk(disk_), ncnt(ncnt_), ex(stage), ey(stage + 27 * g_.nmax), ez(stage + 2 * 27 * g_.nmax), ep(tags),
+          inv_l(list), pay(pay_), lane((int)threadIdx.x), nm(g_.nmax), p(lane % HS), ee(lane / HS) {
+        if (lane < 32) inv_l[lane] = 0;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
+
+    // slot `slot` (< the cell's count where act) of storage cell c_idx, image-shifted
+    __device__ __forceinline__ void load_slot(bool act, int c_idx, int slot, float isx, float isy, float isz, float& ux,
+                                              float& uy, float& uz, PT& up) const {
+        ux = uy = uz = 0.0f;
+        up = pay.none();
+        if (act) {
+            const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)slot * lay_slot()) * DA::kUnit;
+            DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
+            if constexpr (Pay::kOfPosition) up = pay(ux, uy, uz);
+            ux = ux + isx;   // (+0 for the cells that are not wrapped)
+            uy = uy + isy;
+            uz = uz + isz;
+            if constexpr (!Pay::kOfPosition) up = pay(c_idx, slot);
+        }
+    }
+
+    __device__ __forceinline__ void put(bool act, float ux, float uy, float uz, PT up) {
+        const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+        if (act) {
+            const int dst = S + mbcnt64(am);
+            ex[dst] = ux;
+            ey[dst] = uy;
+            ez[dst] = uz;
+            if constexpr (Pay::kStaged) ep[dst] = up;
+        }
+        S += __popcll(am);
+    }
+
+    // the rows of cur go out: four passes of CPP cells x HS slots over its occupied stencil cells
+    __device__ __forceinline__ void issue_rows() {
+        const unsigned long long mo = __builtin_amdgcn_ballot_w64(cur.cnt > 0);
+        ncells = __popcll(mo);
+        if (cur.cnt > 0) inv_l[mbcnt64(mo)] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int q = 0; q < NPMAX; ++q) {
+            const int e = q * CPP + ee;
+            const int src = inv_l[e < ncells ? e : 0];
+            const int c_cnt = __shfl(cur.cnt, src);
+            const int c_idx = __shfl(cur.kc, src);
+            const float isx = __shfl(cur.sx, src), isy = __shfl(cur.sy, src), isz = __shfl(cur.sz, src);
+            vact[q] = e < ncells && p < c_cnt;
+            load_slot(vact[q], c_idx, p, isx, isy, isz, vx[q], vy[q], vz[q], vp[q]);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
+    }
+
+    // stages cur, its rows being in flight: the own cell unfiltered, then stencil cells 1..26
+    // filtered; S = the staged particles.  No fence: the caller's.
+    __device__ __forceinline__ void stage() {
+        float blo[3], bhi[3];
+        pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
+        auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
+        S = 0;
+        // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles, up to
+        // CPP cells per round
+        auto chunks = [&](unsigned long long mg, bool filter) {
+            if constexpr (NSLOT > HS) {
+                for (int s0 = HS; s0 < nm; s0 += HS) {
+                    unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
+                    while (ov) {
+                        int ks = 0, nc = 0;
+                        for (; nc < CPP && ov; ++nc) {
+                            const int kb = (int)__builtin_ctzll(ov);
+                            ov &= ov - 1ull;
+                            ks = ee == nc ? kb : ks;
+                        }
+                        const int c_cnt = __shfl(cur.cnt, ks);
+                        const int c_idx = __shfl(cur.kc, ks);
+                        const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
+                        const int ps = s0 + p;
+                        const bool act = ee < nc && ps < c_cnt;
+                        float ux, uy, uz;
+                        PT up;
+                        load_slot(act, c_idx, ps, isx, isy, isz, ux, uy, uz, up);
+                        put(act && (!filter || near(ux, uy, uz)), ux, uy, uz, up);
+                    }
+                }
+            }
+        };
+        // list entries of the own cell (lane 0 of the stencil)
+        const int e_own = __builtin_amdgcn_readfirstlane(cur.cnt) > 0 ? 1 : 0;
+        put(vact[0] && ee < e_own, vx[0], vy[0], vz[0], vp[0]);   // own slots [0, HS)
+        chunks(1ull, false);                                      // own slots [HS, n)
+#pragma unroll
+        for (int q = 0; q < NPMAX; ++q) {
+            const int e = q * CPP + ee;
+            if (q * CPP < ncells) put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q], vp[q]);
+        }
+        chunks(0x7FFFFFEull, true);   // stencil cells 1..26
+    }
+
+    // The wave's cells, in runs of kPairObsRun with a stride of the grid.  Per cell: stage,
+    // staged(cell, S, n_own) (further LDS the body needs, under the same fence), the next cell's rows,
+    // body(cell, S, n_own).  A body that read the staging arrays ends with a wavefront fence: the next
+    // cell's staging overwrites them.
+    template <class Staged, class Body>
+    __device__ __forceinline__ void run(uint32_t total_cells, Staged&& staged, Body&& body) {
+        const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
+        for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
+            const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
+            cur = pairobs_stencil(g, ncnt, base);
+            issue_rows();
+            nxt = cur;
+            if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
+            for (int c = 0; c < ncl; ++c) {
+                const WalkCell cell{cur.x, cur.y, cur.zg, __builtin_amdgcn_readfirstlane(cur.kc)};
+                const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
+                stage();
+                const int staged_n = S;
+                staged(cell, staged_n, n_own);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                // the next cell's rows go out now and arrive while this cell's body runs
+                if (c + 1 < ncl) {
+                    cur = nxt;
+                    issue_rows();
+                    if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
+                }
+                body(cell, staged_n, n_own);
+            }
+        }
+    }
+    template <class Body>
+    __device__ __forceinline__ void run(uint32_t total_cells, Body&& body) {
+        run(total_cells, [](const WalkCell&, int, int) {}, body);
+    }
+};
+
+// The ordered pairs (i, j) of a staged cell through the ring of in-cutoff r2 values: lane j holds
+// staged partner j (blocks of 64), own particle i (staged first: lane i of block 0) is broadcast by
+// readlane, j == i is skipped; the in-cutoff r2 are compacted into `ring` (kPairObsRing floats) and
+// term(r2) runs on full waves of them, one pair per lane.  n_pairs counts the pairs.
+template <class Term>
+__device__ __forceinline__ void ring_pairs(const float* ex_, const float* ey_, const float* ez_, float* ring, int S,
+                                           int n_own, float rc2, unsigned long long& n_pairs, Term&& term) {
+    constexpr int RM = kPairObsRing - 1;
+    const int lane = threadIdx.x;
+    int head = 0, C = 0;   // ring: entries [head, head + C) mod kPairObsRing
+    auto drain = [&](int lim) {
+        if (lane < lim) term(ring[(head + lane) & RM]);
+        head = (head + 64) & RM;
+        C -= lim;
+    };
+    const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+    auto block = [&](int jb, auto first_c) {
+        constexpr bool kFirst = decltype(first_c)::value;
+        const int j = jb + lane;
+        const bool vj = j < S;
+        const int jj = vj ? j : 0;
+        float xj = ox, yj = oy, zj = oz;
+        if constexpr (!kFirst) {
+            xj = ex_[jj];
+            yj = ey_[jj];
+            zj = ez_[jj];
+        }
+        const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
+        for (int i = 0; i < n_own; ++i) {
+            const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+            const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+            const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+            const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
+            unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rc2) & vm;
+            if constexpr (kFirst) im &= ~(1ull << i);
+            if (__builtin_amdgcn_inverse_ballot_w64(im)) ring[(head + C + mbcnt64(im)) & RM] = r2;
+            const int k = __popcll(im);
+            C += k;   // C < 64 + 64 <= ring size
+            n_pairs += (unsigned long long)k;
+            if (C >= 64) drain(64);
+        }
+    };
+    block(0, std::true_type{});
+    for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
+    if (C > 0) drain(C);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+}
+
 template <int NSLOT, bool OFF32>
 __global__ __launch_bounds__(kWave) void k_pairobs(DevGeom g, const float* __restrict__ disk,
                                                    const int16_t* __restrict__ ncnt,
                                                    unsigned long long* __restrict__ acc, uint32_t total_cells,
                                                    float rmax2, float bscale, int nbins) {
     extern __shared__ __attribute__((aligned(16))) float psm[];
-    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
-    constexpr int CPP = kWave / HS;    // cells per staging pass
-    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
-    using DA = DiskAddr<OFF32>;
     const int lane = threadIdx.x;
     const int nm = g.nmax;
     const int cap = 27 * nm;
@@ -2586,166 +2843,21 @@ __global__ __launch_bounds__(kWave) void k_pairobs(DevGeom g, const float* __res
     float* ring = psm + 3 * cap;
     int* inv_l = (int*)(ring + kPairObsRing);      // list entry -> stencil lane (32 ints)
     unsigned* hist = (unsigned*)(inv_l + 32);      // nbins counters of this wave
-    const int p = lane % HS;
-    const int ee = lane / HS;
     const float rc2 = g.rc2;
     long long sum = 0;                             // per lane
     unsigned long long n_pairs = 0, n_part = 0;    // wave-uniform
     for (int b = lane; b < nbins; b += kWave) hist[b] = 0u;
-    if (lane < 32) inv_l[lane] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-
-    // rows of the cell in flight: slots [0, HS) of its occupied stencil cells (own cell: entry 0 when
-    // occupied), in registers
-    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
-    bool vact[NPMAX];
-    int ncells = 0;
-    auto issue_rows = [&](const PairObsStencil& st) {
-        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
-        ncells = __popcll(mo);
-        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-        for (int q = 0; q < NPMAX; ++q) {
-            const int e = q * CPP + ee;
-            const int src = inv_l[e < ncells ? e : 0];
-            const int c_cnt = __shfl(st.cnt, src);
-            const int c_idx = __shfl(st.kc, src);
-            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
-            vact[q] = e < ncells && p < c_cnt;
-            vx[q] = vy[q] = vz[q] = 0.0f;
-            if (vact[q]) {
-                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
-                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
-                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
-                vy[q] = vy[q] + isy;
-                vz[q] = vz[q] + isz;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
-    };
-
-    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
-    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
-        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
-        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
-        issue_rows(cur);
-        PairObsStencil nxt = cur;
-        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
-        for (int c = 0; c < ncl; ++c) {
-            // ---- stage cell c: own particles first (lanes of list entry 0 and the own chunks), then
-            //      the filtered partners
-            float blo[3], bhi[3];
-            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
-            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
-            int S = 0;
-            auto put = [&](bool act, float ux, float uy, float uz) {
-                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
-                if (act) {
-                    const int dst = S + mbcnt64(am);
-                    ex_[dst] = ux;
-                    ey_[dst] = uy;
-                    ez_[dst] = uz;
-                }
-                S += __popcll(am);
-            };
-            // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles
-            auto chunks = [&](unsigned long long mg, bool filter) {
-                if constexpr (NSLOT > HS) {
-                    for (int s0 = HS; s0 < nm; s0 += HS) {
-                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
-                        while (ov) {
-                            int ks = 0, nc = 0;
-                            for (; nc < CPP && ov; ++nc) {
-                                const int kb = (int)__builtin_ctzll(ov);
-                                ov &= ov - 1ull;
-                                ks = ee == nc ? kb : ks;
-                            }
-                            const int c_cnt = __shfl(cur.cnt, ks);
-                            const int c_idx = __shfl(cur.kc, ks);
-                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
-                            const int ps = s0 + p;
-                            const bool act = ee < nc && ps < c_cnt;
-                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-                            if (act) {
-                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
-                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
-                                ux = ux + isx;
-                                uy = uy + isy;
-                                uz = uz + isz;
-                            }
-                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz);
-                        }
-                    }
-                }
-            };
-            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
-            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
-            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0]);             // own slots [0, HS)
-            chunks(1ull, false);                                          // own slots [HS, n)
-#pragma unroll
-            for (int q = 0; q < NPMAX; ++q) {
-                const int e = q * CPP + ee;
-                if (q * CPP < ncells) put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q]);
-            }
-            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            // ---- the next cell's rows go out now and arrive while this cell's pairs run
-            if (c + 1 < ncl) {
-                cur = nxt;
-                issue_rows(cur);
-                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
-            }
-            n_part += (unsigned long long)n_own;
-            if (n_own == 0) continue;
-            // ---- ordered pairs (i, j): lane j holds staged partner j (blocks of 64), own particle
-            //      i (staged first: lane i of block 0) broadcast by readlane; j == i skipped
-            constexpr int RM = kPairObsRing - 1;
-            int head = 0, C = 0;   // ring: entries [head, head + C) mod kPairObsRing
-            auto drain = [&](int lim) {
-                if (lane < lim) {
-                    const float r2 = ring[(head + lane) & RM];
-                    sum += pmc_to_fixed_f32(pmc_virial_term(r2));
-                    if (r2 < rmax2)
-                        (void)__hip_atomic_fetch_add(&hist[pmc_pairobs_bin(r2, bscale, nbins)], 1u, __ATOMIC_RELAXED,
-                                                     __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                head = (head + 64) & RM;
-                C -= lim;
-            };
-            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
-            auto block = [&](int jb, auto first_c) {
-                constexpr bool kFirst = decltype(first_c)::value;
-                const int j = jb + lane;
-                const bool vj = j < S;
-                const int jj = vj ? j : 0;
-                float xj = ox, yj = oy, zj = oz;
-                if constexpr (!kFirst) {
-                    xj = ex_[jj];
-                    yj = ey_[jj];
-                    zj = ez_[jj];
-                }
-                const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
-                for (int i = 0; i < n_own; ++i) {
-                    const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
-                    const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
-                    const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
-                    const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
-                    unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rc2) & vm;
-                    if constexpr (kFirst) im &= ~(1ull << i);
-                    if (__builtin_amdgcn_inverse_ballot_w64(im)) ring[(head + C + mbcnt64(im)) & RM] = r2;
-                    const int k = __popcll(im);
-                    C += k;   // C < 64 + 64 <= ring size
-                    n_pairs += (unsigned long long)k;
-                    if (C >= 64) drain(64);
-                }
-            };
-            block(0, std::true_type{});
-            for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
-            if (C > 0) drain(C);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
-        }
-    }
+    CellWalk<NSLOT, OFF32> walk(g, disk, ncnt, ex_, nullptr, inv_l);
+    walk.run(total_cells, [&](const WalkCell&, int S, int n_own) {
+        n_part += (unsigned long long)n_own;
+        if (n_own == 0) return;
+        ring_pairs(ex_, ey_, ez_, ring, S, n_own, rc2, n_pairs, [&](float r2) {
+            sum += pmc_to_fixed_f32(pmc_virial_term(r2));
+            if (r2 < rmax2)
+                (void)__hip_atomic_fetch_add(&hist[pmc_pairobs_bin(r2, bscale, nbins)], 1u, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+        });
+    });
     // ---- flush: wave sums (int64, exact in any order), this wave's nonzero bins
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
@@ -2761,11 +2873,9 @@ __global__ __launch_bounds__(kWave) void k_pairobs(DevGeom g, const float* __res
 // ------------------------------------------------------------------------------------------
 // isobaric volume moves (include/pmc_npt.h).
 //
-// k_npt_sums is k_pairobs' per-cell form without the histogram: the same stencil (pairobs_stencil),
-// the same staging (rows of 8 slots, chunks for the fuller cells, own cell first, the pmc_box_d2
-// filter and the 27 * nmax LDS capacity), the same ring of in-cutoff r2 values; a drained pair adds
-// fixed(r^-12) and fixed(r^-6) to two per-lane int64 sums.  A wave flushes once into one of
-// kNptCopies accumulator copies ([s12, s6, pairs, particles]) the host sums.  Integer sums only:
+// k_npt_sums is k_pairobs without the histogram: the cell walk (CellWalk) and the ring of in-cutoff
+// r2 values (ring_pairs); a drained pair adds fixed(r^-12) and fixed(r^-6) to two per-lane int64
+// sums.  A wave flushes once into one of kNptCopies accumulator copies ([s12, s6, pairs, particles]) the host sums.  Integer sums only:
 // equal to tests/npt_ref.c bit for bit.
 // ------------------------------------------------------------------------------------------
 template <int NSLOT, bool OFF32>
@@ -2773,10 +2883,6 @@ __global__ __launch_bounds__(kWave) void k_npt_sums(DevGeom g, const float* __re
                                                     const int16_t* __restrict__ ncnt,
                                                     unsigned long long* __restrict__ acc, uint32_t total_cells) {
     extern __shared__ __attribute__((aligned(16))) float psm[];
-    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
-    constexpr int CPP = kWave / HS;    // cells per staging pass
-    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
-    using DA = DiskAddr<OFF32>;
     const int lane = threadIdx.x;
     const int nm = g.nmax;
     const int cap = 27 * nm;
@@ -2785,160 +2891,20 @@ __global__ __launch_bounds__(kWave) void k_npt_sums(DevGeom g, const float* __re
     float* ez_ = psm + 2 * cap;
     float* ring = psm + 3 * cap;
     int* inv_l = (int*)(ring + kPairObsRing);      // list entry -> stencil lane (32 ints)
-    const int p = lane % HS;
-    const int ee = lane / HS;
     const float rc2 = g.rc2;
     long long sum12 = 0, sum6 = 0;                 // per lane
     unsigned long long n_pairs = 0, n_part = 0;    // wave-uniform
-    if (lane < 32) inv_l[lane] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-
-    // rows of the cell in flight (k_pairobs' issue_rows): slots [0, HS) of its occupied stencil cells
-    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
-    bool vact[NPMAX];
-    int ncells = 0;
-    auto issue_rows = [&](const PairObsStencil& st) {
-        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
-        ncells = __popcll(mo);
-        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-        for (int q = 0; q < NPMAX; ++q) {
-            const int e = q * CPP + ee;
-            const int src = inv_l[e < ncells ? e : 0];
-            const int c_cnt = __shfl(st.cnt, src);
-            const int c_idx = __shfl(st.kc, src);
-            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
-            vact[q] = e < ncells && p < c_cnt;
-            vx[q] = vy[q] = vz[q] = 0.0f;
-            if (vact[q]) {
-                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
-                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
-                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
-                vy[q] = vy[q] + isy;
-                vz[q] = vz[q] + isz;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
-    };
-
-    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
-    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
-        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
-        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
-        issue_rows(cur);
-        PairObsStencil nxt = cur;
-        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
-        for (int c = 0; c < ncl; ++c) {
-            // ---- stage cell c (k_pairobs' staging): own particles first, then the filtered partners
-            float blo[3], bhi[3];
-            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
-            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
-            int S = 0;
-            auto put = [&](bool act, float ux, float uy, float uz) {
-                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
-                if (act) {
-                    const int dst = S + mbcnt64(am);
-                    ex_[dst] = ux;
-                    ey_[dst] = uy;
-                    ez_[dst] = uz;
-                }
-                S += __popcll(am);
-            };
-            auto chunks = [&](unsigned long long mg, bool filter) {
-                if constexpr (NSLOT > HS) {
-                    for (int s0 = HS; s0 < nm; s0 += HS) {
-                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
-                        while (ov) {
-                            int ks = 0, nc = 0;
-                            for (; nc < CPP && ov; ++nc) {
-                                const int kb = (int)__builtin_ctzll(ov);
-                                ov &= ov - 1ull;
-                                ks = ee == nc ? kb : ks;
-                            }
-                            const int c_cnt = __shfl(cur.cnt, ks);
-                            const int c_idx = __shfl(cur.kc, ks);
-                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
-                            const int ps = s0 + p;
-                            const bool act = ee < nc && ps < c_cnt;
-                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-                            if (act) {
-                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
-                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
-                                ux = ux + isx;
-                                uy = uy + isy;
-                                uz = uz + isz;
-                            }
-                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz);
-                        }
-                    }
-                }
-            };
-            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
-            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
-            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0]);             // own slots [0, HS)
-            chunks(1ull, false);                                          // own slots [HS, n)
-#pragma unroll
-            for (int q = 0; q < NPMAX; ++q) {
-                const int e = q * CPP + ee;
-                if (q * CPP < ncells) put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q]);
-            }
-            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            // ---- the next cell's rows go out now and arrive while this cell's pairs run
-            if (c + 1 < ncl) {
-                cur = nxt;
-                issue_rows(cur);
-                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
-            }
-            n_part += (unsigned long long)n_own;
-            if (n_own == 0) continue;
-            // ---- ordered pairs (i, j), k_pairobs' blocks and ring; j == i skipped
-            constexpr int RM = kPairObsRing - 1;
-            int head = 0, C = 0;   // ring: entries [head, head + C) mod kPairObsRing
-            auto drain = [&](int lim) {
-                if (lane < lim) {
-                    float p6, p12;
-                    pmc_npt_terms(ring[(head + lane) & RM], &p6, &p12);
-                    sum6 += pmc_to_fixed_f32(p6);
-                    sum12 += pmc_to_fixed_f32(p12);
-                }
-                head = (head + 64) & RM;
-                C -= lim;
-            };
-            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
-            auto block = [&](int jb, auto first_c) {
-                constexpr bool kFirst = decltype(first_c)::value;
-                const int j = jb + lane;
-                const bool vj = j < S;
-                const int jj = vj ? j : 0;
-                float xj = ox, yj = oy, zj = oz;
-                if constexpr (!kFirst) {
-                    xj = ex_[jj];
-                    yj = ey_[jj];
-                    zj = ez_[jj];
-                }
-                const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
-                for (int i = 0; i < n_own; ++i) {
-                    const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
-                    const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
-                    const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
-                    const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
-                    unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rc2) & vm;
-                    if constexpr (kFirst) im &= ~(1ull << i);
-                    if (__builtin_amdgcn_inverse_ballot_w64(im)) ring[(head + C + mbcnt64(im)) & RM] = r2;
-                    const int k = __popcll(im);
-                    C += k;   // C < 64 + 64 <= ring size
-                    n_pairs += (unsigned long long)k;
-                    if (C >= 64) drain(64);
-                }
-            };
-            block(0, std::true_type{});
-            for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
-            if (C > 0) drain(C);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
-        }
-    }
+    CellWalk<NSLOT, OFF32> walk(g, disk, ncnt, ex_, nullptr, inv_l);
+    walk.run(total_cells, [&](const WalkCell&, int S, int n_own) {
+        n_part += (unsigned long long)n_own;
+        if (n_own == 0) return;
+        ring_pairs(ex_, ey_, ez_, ring, S, n_own, rc2, n_pairs, [&](float r2) {
+            float p6, p12;
+            pmc_npt_terms(r2, &p6, &p12);
+            sum6 += pmc_to_fixed_f32(p6);
+            sum12 += pmc_to_fixed_f32(p12);
+        });
+    });
     // ---- flush: wave sums (int64, exact in any order)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -3040,10 +3006,8 @@ __global__ __launch_bounds__(kRescaleThreads) void k_rescale(DevGeom g, float* _
 // cluster analysis (include/pmc_cluster.h): degrees, core particles and the connected components of
 // the core particles under "bonded in either direction", in four launches on one stream.
 //
-// k_cluster_walk<.., false> (degree) and <.., true> (link) are k_pairobs' per-cell form: the same
-// stencil (pairobs_stencil), the same staging (rows of 8 slots, chunks for the fuller cells, own cell
-// first, the pmc_box_d2 filter -- conservative for r_bond <= w -- and the 27 * nmax LDS capacity),
-// the same fixed grid of waves over runs of kPairObsRun cells.  Degree: lane i keeps the degree of
+// k_cluster_walk<.., false> (degree) and <.., true> (link) are cell walks (CellWalk; its
+// pmc_box_d2 filter is conservative for r_bond <= w).  Degree: lane i keeps the degree of
 // own particle i (ballot / popcount per partner block), then writes deg[id] and the initial
 // parent[id] (id if core, the memset's -1 otherwise) and bins the degree in the wave's LDS
 // histogram.  Link: every staged particle carries a tag beside its position (its id if it is core,
@@ -3101,10 +3065,6 @@ __global__ __launch_bounds__(kWave) void k_cluster_walk(DevGeom g, const float* 
                                                         float rb2, int min_nb, int* __restrict__ parent,
                                                         uint16_t* __restrict__ deg) {
     extern __shared__ __attribute__((aligned(16))) float csm[];
-    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
-    constexpr int CPP = kWave / HS;    // cells per staging pass
-    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
-    using DA = DiskAddr<OFF32>;
     const int lane = threadIdx.x;
     const int nm = g.nmax;
     const int cap = 27 * nm;
@@ -3114,187 +3074,77 @@ __global__ __launch_bounds__(kWave) void k_cluster_walk(DevGeom g, const float* 
     int* et_ = (int*)(csm + 3 * cap);              // link: tag of a staged particle (id if core, else -1)
     int* inv_l = et_ + (LINK ? cap : 0);           // list entry -> stencil lane (32 ints)
     unsigned* hist = (unsigned*)(inv_l + 32);      // degree: kClusterDegBins counters of this wave
-    const int p = lane % HS;
-    const int ee = lane / HS;
     unsigned long long n_pairs = 0, n_part = 0, n_core = 0;    // wave-uniform
     if constexpr (!LINK)
         for (int b = lane; b < kClusterDegBins; b += kWave) hist[b] = 0u;
-    if (lane < 32) inv_l[lane] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-
-    auto tag_of = [&](int id) {
-        if constexpr (LINK) return (int)deg[id] >= min_nb ? id : -1;
-        else return 0;
-    };
-
-    // rows of the cell in flight (k_pairobs' issue_rows): slots [0, HS) of its occupied stencil cells
-    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
-    int vt[NPMAX];
-    bool vact[NPMAX];
-    int ncells = 0;
-    auto issue_rows = [&](const PairObsStencil& st) {
-        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
-        ncells = __popcll(mo);
-        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-        for (int q = 0; q < NPMAX; ++q) {
-            const int e = q * CPP + ee;
-            const int src = inv_l[e < ncells ? e : 0];
-            const int c_cnt = __shfl(st.cnt, src);
-            const int c_idx = __shfl(st.kc, src);
-            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
-            vact[q] = e < ncells && p < c_cnt;
-            vx[q] = vy[q] = vz[q] = 0.0f;
-            vt[q] = -1;
-            if (vact[q]) {
-                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
-                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
-                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
-                vy[q] = vy[q] + isy;
-                vz[q] = vz[q] + isz;
-                vt[q] = tag_of(c_idx * nm + p);
+    // link: the tag of the particle in (storage cell, slot)
+    const auto tag = tag_payload<LINK>([&](int cell, int slot) {
+        const int id = cell * nm + slot;
+        return (int)deg[id] >= min_nb ? id : -1;
+    });
+    CellWalk<NSLOT, OFF32, decltype(tag)> walk(g, disk, ncnt, ex_, et_, inv_l, tag);
+    walk.run(total_cells, [&](const WalkCell& cell, int S, int n_own) {
+        const int id0 = cell.kc * nm;   // id of the own cell's slot 0
+        n_part += (unsigned long long)n_own;
+        if (n_own == 0) return;
+        // ---- ordered pairs (i, j): lane j holds staged partner j (blocks of 64), own particle
+        //      i (staged first, in slot order: lane i of block 0) broadcast by readlane; j == i skipped
+        const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+        int ot = -1;                                                   // link: the own particles' tags
+        if constexpr (LINK) ot = et_[lane];
+        int mydeg = 0;                                                 // degree: lane i, own particle i
+        auto block = [&](int jb, auto first_c) {
+            constexpr bool kFirst = decltype(first_c)::value;
+            const int j = jb + lane;
+            const bool vj = j < S;
+            const int jj = vj ? j : 0;
+            float xj = ox, yj = oy, zj = oz;
+            int tj = ot;
+            if constexpr (!kFirst) {
+                xj = ex_[jj];
+                yj = ey_[jj];
+                zj = ez_[jj];
+                if constexpr (LINK) tj = et_[jj];
             }
+            const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
+            for (int i = 0; i < n_own; ++i) {
+                int ti = 0;
+                if constexpr (LINK) {
+                    ti = __builtin_amdgcn_readlane(ot, i);
+                    if (ti < 0) continue;   // wave-uniform: a particle that is not core has no edges
+                }
+                const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+                const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+                const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+                const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
+                unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rb2) & vm;
+                if constexpr (kFirst) im &= ~(1ull << i);
+                if constexpr (LINK) {
+                    const bool hit = ((im >> lane) & 1ull) && tj >= 0;
+                    n_pairs += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(hit));
+                    if (hit) cluster_unite(parent, ti, tj);
+                } else {
+                    const int k = __popcll(im);
+                    n_pairs += (unsigned long long)k;
+                    mydeg += lane == i ? k : 0;
+                }
+            }
+        };
+        block(0, std::true_type{});
+        for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
+        if constexpr (!LINK) {
+            const bool own = lane < n_own;
+            const bool core = own && mydeg >= min_nb;
+            if (own) {
+                deg[id0 + lane] = (uint16_t)mydeg;   // at most 27 * 64 - 1
+                if (core) parent[id0 + lane] = id0 + lane;
+                (void)__hip_atomic_fetch_add(&hist[pmc_cluster_deg_bin(mydeg)], 1u, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            n_core += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(core));
         }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
-    };
-
-    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
-    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
-        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
-        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
-        issue_rows(cur);
-        PairObsStencil nxt = cur;
-        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
-        for (int c = 0; c < ncl; ++c) {
-            // ---- stage cell c (k_pairobs' staging): own particles first, then the filtered partners
-            float blo[3], bhi[3];
-            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
-            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
-            int S = 0;
-            auto put = [&](bool act, float ux, float uy, float uz, int ut) {
-                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
-                if (act) {
-                    const int dst = S + mbcnt64(am);
-                    ex_[dst] = ux;
-                    ey_[dst] = uy;
-                    ez_[dst] = uz;
-                    if constexpr (LINK) et_[dst] = ut;
-                }
-                S += __popcll(am);
-            };
-            // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles
-            auto chunks = [&](unsigned long long mg, bool filter) {
-                if constexpr (NSLOT > HS) {
-                    for (int s0 = HS; s0 < nm; s0 += HS) {
-                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
-                        while (ov) {
-                            int ks = 0, nc = 0;
-                            for (; nc < CPP && ov; ++nc) {
-                                const int kb = (int)__builtin_ctzll(ov);
-                                ov &= ov - 1ull;
-                                ks = ee == nc ? kb : ks;
-                            }
-                            const int c_cnt = __shfl(cur.cnt, ks);
-                            const int c_idx = __shfl(cur.kc, ks);
-                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
-                            const int ps = s0 + p;
-                            const bool act = ee < nc && ps < c_cnt;
-                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-                            int ut = -1;
-                            if (act) {
-                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
-                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
-                                ux = ux + isx;
-                                uy = uy + isy;
-                                uz = uz + isz;
-                                ut = tag_of(c_idx * nm + ps);
-                            }
-                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz, ut);
-                        }
-                    }
-                }
-            };
-            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
-            const int id0 = __builtin_amdgcn_readfirstlane(cur.kc) * nm;  // id of the own cell's slot 0
-            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
-            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0], vt[0]);      // own slots [0, HS)
-            chunks(1ull, false);                                          // own slots [HS, n)
-#pragma unroll
-            for (int q = 0; q < NPMAX; ++q) {
-                const int e = q * CPP + ee;
-                if (q * CPP < ncells)
-                    put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q], vt[q]);
-            }
-            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            // ---- the next cell's rows go out now and arrive while this cell's pairs run
-            if (c + 1 < ncl) {
-                cur = nxt;
-                issue_rows(cur);
-                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
-            }
-            n_part += (unsigned long long)n_own;
-            if (n_own == 0) continue;
-            // ---- ordered pairs (i, j): lane j holds staged partner j (blocks of 64), own particle
-            //      i (staged first, in slot order: lane i of block 0) broadcast by readlane; j == i skipped
-            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
-            int ot = -1;                                                   // link: the own particles' tags
-            if constexpr (LINK) ot = et_[lane];
-            int mydeg = 0;                                                 // degree: lane i, own particle i
-            auto block = [&](int jb, auto first_c) {
-                constexpr bool kFirst = decltype(first_c)::value;
-                const int j = jb + lane;
-                const bool vj = j < S;
-                const int jj = vj ? j : 0;
-                float xj = ox, yj = oy, zj = oz;
-                int tj = ot;
-                if constexpr (!kFirst) {
-                    xj = ex_[jj];
-                    yj = ey_[jj];
-                    zj = ez_[jj];
-                    if constexpr (LINK) tj = et_[jj];
-                }
-                const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
-                for (int i = 0; i < n_own; ++i) {
-                    int ti = 0;
-                    if constexpr (LINK) {
-                        ti = __builtin_amdgcn_readlane(ot, i);
-                        if (ti < 0) continue;   // wave-uniform: a particle that is not core has no edges
-                    }
-                    const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
-                    const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
-                    const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
-                    const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
-                    unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rb2) & vm;
-                    if constexpr (kFirst) im &= ~(1ull << i);
-                    if constexpr (LINK) {
-                        const bool hit = ((im >> lane) & 1ull) && tj >= 0;
-                        n_pairs += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(hit));
-                        if (hit) cluster_unite(parent, ti, tj);
-                    } else {
-                        const int k = __popcll(im);
-                        n_pairs += (unsigned long long)k;
-                        mydeg += lane == i ? k : 0;
-                    }
-                }
-            };
-            block(0, std::true_type{});
-            for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
-            if constexpr (!LINK) {
-                const bool own = lane < n_own;
-                const bool core = own && mydeg >= min_nb;
-                if (own) {
-                    deg[id0 + lane] = (uint16_t)mydeg;   // at most 27 * 64 - 1
-                    if (core) parent[id0 + lane] = id0 + lane;
-                    (void)__hip_atomic_fetch_add(&hist[pmc_cluster_deg_bin(mydeg)], 1u, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                n_core += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(core));
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
-        }
-    }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+    });
     // ---- flush: degree [bonds, particles, core, -, hdeg[]]; link [-, -, -, core_bonds]
     unsigned long long* mine = acc + (size_t)(blockIdx.x & (kClusterCopies - 1)) * (size_t)(kClusterHead + kClusterDegBins);
     if constexpr (LINK) {
@@ -3373,9 +3223,10 @@ __global__ __launch_bounds__(256) void k_cluster_count(const int* __restrict__ p
 }
 
 // ------------------------------------------------------------------------------------------
-// bond-orientational order (include/pmc_boo.h): two further walks in k_cluster_walk's per-cell form
-// (the same stencil, staging, chunks, pmc_box_d2 filter, LDS capacity and fixed grid), then the
-// cluster analysis' own link, flatten and count launches on the connections.
+// bond-orientational order (include/pmc_boo.h): two further walks that keep a private copy of the
+// cell walk (CellWalk's stencil, staging order, chunks, filter and capacity; on the shared form they
+// ran 1-2 % slower), then the cluster analysis' own link, flatten and count launches on
+// the connections.
 //
 // k_boo_accum<.., L>: lane j holds staged partner j, own particle i is broadcast; hits are sparse
 // (about 12 of 130 staged partners at r_bond 1.5), so the harmonics run on the hit lanes only, under
@@ -3427,7 +3278,8 @@ __device__ __forceinline__ void boo_walk(const DevGeom& g, const float* __restri
     if (lane < 32) inv_l[lane] = 0;
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 
-    // rows of the cell in flight (k_cluster_walk's issue_rows): slots [0, HS) of its occupied stencil cells
+    // rows of the cell in flight (CellWalk::issue_rows, with the particle id): slots [0, HS) of its
+    // occupied stencil cells
     float vx[NPMAX], vy[NPMAX], vz[NPMAX];
     int vt[NPMAX];
     bool vact[NPMAX];
@@ -3467,7 +3319,7 @@ __device__ __forceinline__ void boo_walk(const DevGeom& g, const float* __restri
         PairObsStencil nxt = cur;
         if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
         for (int c = 0; c < ncl; ++c) {
-            // ---- stage cell c (k_cluster_walk's staging): own particles first, then the filtered partners
+            // ---- stage cell c (CellWalk::stage): own particles first, then the filtered partners
             float blo[3], bhi[3];
             pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
             auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
@@ -3713,9 +3565,8 @@ __global__ __launch_bounds__(kWave) void k_boo_conn(DevGeom g, const float* __re
 // place: the analysis has no further use for Q_m, and a second record scratch would cost another 64
 // bytes per slot.  N and deg stay where they are.
 //
-// k_boo_avg<.., L>: k_boo_conn's form (boo_walk's stencil, staging, chunks, pmc_box_d2 filter; every
-// staged particle carries its id).  The blocks of partners without a hit are skipped wave-uniformly;
-// on a hit the lane gathers the partner's u by id (2l + 1 ints of its 64-byte record) and adds them
+// k_boo_avg<.., L>: a cell walk (CellWalk) in which every staged particle carries its id.  The
+// blocks of partners without a hit are skipped wave-uniformly; on a hit the lane gathers the partner's u by id (2l + 1 ints of its 64-byte record) and adds them
 // to the LDS table [own slot][2l + 1] with LDS integer atomics (the hit lanes of one own particle
 // share its row, as in k_boo_accum: integer sums do not depend on the order in which the adds
 // land).  Lane i then adds its own u_m(i), forms
@@ -3756,10 +3607,6 @@ __global__ __launch_bounds__(kWave) void k_boo_avg(DevGeom g, const float* __res
     static_assert(L == 4 || L == 6, "l is 4 or 6");
     extern __shared__ __attribute__((aligned(16))) float csm[];
     constexpr int NT = 2 * L + 1;      // ints per own particle in the LDS table
-    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
-    constexpr int CPP = kWave / HS;    // cells per staging pass
-    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
-    using DA = DiskAddr<OFF32>;
     const int lane = threadIdx.x;
     const int nm = g.nmax;
     const int cap = 27 * nm;
@@ -3770,201 +3617,94 @@ __global__ __launch_bounds__(kWave) void k_boo_avg(DevGeom g, const float* __res
     int* inv_l = et_ + cap;                        // list entry -> stencil lane (32 ints)
     int* tab = inv_l + 32;                         // [kWave][NT]: A_m of the own particles
     unsigned* hist = (unsigned*)(tab + kWave * NT);   // nq bins of q-bar_l
-    const int p = lane % HS;
-    const int ee = lane / HS;
     unsigned long long n_pairs = 0, n_part = 0;    // wave-uniform
     for (int b = lane; b < nq; b += kWave) hist[b] = 0u;
-    if (lane < 32) inv_l[lane] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-
-    // rows of the cell in flight (boo_walk's issue_rows): slots [0, HS) of its occupied stencil cells
-    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
-    int vt[NPMAX];
-    bool vact[NPMAX];
-    int ncells = 0;
-    auto issue_rows = [&](const PairObsStencil& st) {
-        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
-        ncells = __popcll(mo);
-        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-        for (int q = 0; q < NPMAX; ++q) {
-            const int e = q * CPP + ee;
-            const int src = inv_l[e < ncells ? e : 0];
-            const int c_cnt = __shfl(st.cnt, src);
-            const int c_idx = __shfl(st.kc, src);
-            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
-            vact[q] = e < ncells && p < c_cnt;
-            vx[q] = vy[q] = vz[q] = 0.0f;
-            vt[q] = -1;
-            if (vact[q]) {
-                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
-                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
-                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
-                vy[q] = vy[q] + isy;
-                vz[q] = vz[q] + isz;
-                vt[q] = c_idx * nm + p;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
+    const auto tag = tag_payload([&](int cell, int slot) { return cell * nm + slot; });
+    CellWalk<NSLOT, OFF32, decltype(tag)> walk(g, disk, ncnt, ex_, et_, inv_l, tag);
+    // ---- the own particles' table, zeroed
+    auto zero_table = [&](const WalkCell&, int, int n_own) {
+        for (int k = lane; k < n_own * NT; k += kWave) tab[k] = 0;
     };
-
-    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
-    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
-        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
-        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
-        issue_rows(cur);
-        PairObsStencil nxt = cur;
-        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
-        for (int c = 0; c < ncl; ++c) {
-            // ---- stage cell c (boo_walk's staging): own particles first, then the filtered partners
-            float blo[3], bhi[3];
-            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
-            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
-            int S = 0;
-            auto put = [&](bool act, float ux, float uy, float uz, int ut) {
-                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
-                if (act) {
-                    const int dst = S + mbcnt64(am);
-                    ex_[dst] = ux;
-                    ey_[dst] = uy;
-                    ez_[dst] = uz;
-                    et_[dst] = ut;
-                }
-                S += __popcll(am);
-            };
-            // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles
-            auto chunks = [&](unsigned long long mg, bool filter) {
-                if constexpr (NSLOT > HS) {
-                    for (int s0 = HS; s0 < nm; s0 += HS) {
-                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
-                        while (ov) {
-                            int ks = 0, nc = 0;
-                            for (; nc < CPP && ov; ++nc) {
-                                const int kb = (int)__builtin_ctzll(ov);
-                                ov &= ov - 1ull;
-                                ks = ee == nc ? kb : ks;
-                            }
-                            const int c_cnt = __shfl(cur.cnt, ks);
-                            const int c_idx = __shfl(cur.kc, ks);
-                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
-                            const int ps = s0 + p;
-                            const bool act = ee < nc && ps < c_cnt;
-                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-                            int ut = -1;
-                            if (act) {
-                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
-                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
-                                ux = ux + isx;
-                                uy = uy + isy;
-                                uz = uz + isz;
-                                ut = c_idx * nm + ps;
-                            }
-                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz, ut);
-                        }
-                    }
-                }
-            };
-            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
-            const int id0 = __builtin_amdgcn_readfirstlane(cur.kc) * nm;  // id of the own cell's slot 0
-            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
-            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0], vt[0]);      // own slots [0, HS)
-            chunks(1ull, false);                                          // own slots [HS, n)
-#pragma unroll
-            for (int q = 0; q < NPMAX; ++q) {
-                const int e = q * CPP + ee;
-                if (q * CPP < ncells)
-                    put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q], vt[q]);
+    walk.run(total_cells, zero_table, [&](const WalkCell& cell, int S, int n_own) {
+        const int id0 = cell.kc * nm;   // id of the own cell's slot 0
+        const bool own = lane < n_own;
+        n_part += (unsigned long long)n_own;
+        if (n_own == 0) {
+            if constexpr (L == 4) {
+                if (lane < nm) *(int4*)(slot_out + (size_t)(id0 + lane) * kBooAvgSlot) = make_int4(0, 0, 0, 0);
             }
-            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
-            // ---- the own particles' table, zeroed
-            const bool own = lane < n_own;
-            for (int k = lane; k < n_own * NT; k += kWave) tab[k] = 0;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            // ---- the next cell's rows go out now and arrive while this cell's pairs run
-            if (c + 1 < ncl) {
-                cur = nxt;
-                issue_rows(cur);
-                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
-            }
-            n_part += (unsigned long long)n_own;
-            if (n_own == 0) {
-                if constexpr (L == 4) {
-                    if (lane < nm) *(int4*)(slot_out + (size_t)(id0 + lane) * kBooAvgSlot) = make_int4(0, 0, 0, 0);
-                }
-                continue;
-            }
-            // ---- ordered pairs (i, j): lane j holds staged partner j (blocks of 64), own particle
-            //      i (staged first, in slot order: lane i of block 0) broadcast by readlane; j == i skipped
-            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
-            const int ot = et_[lane];
-            int mydeg = 0;                                                 // lane i: deg(i)
-            auto block = [&](int jb, auto first_c) {
-                constexpr bool kFirst = decltype(first_c)::value;
-                const int j = jb + lane;
-                const bool vj = j < S;
-                const int jj = vj ? j : 0;
-                float xj = ox, yj = oy, zj = oz;
-                int tj = ot;
-                if constexpr (!kFirst) {
-                    xj = ex_[jj];
-                    yj = ey_[jj];
-                    zj = ez_[jj];
-                    tj = et_[jj];
-                }
-                const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
-                for (int i = 0; i < n_own; ++i) {
-                    const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
-                    const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
-                    const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
-                    const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
-                    unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rb2) & vm;
-                    if constexpr (kFirst) im &= ~(1ull << i);
-                    if (im == 0ull) continue;   // wave-uniform
-                    if ((im >> lane) & 1ull) {
-                        // a hit lane holds a staged particle: tj is the id of a slot below its cell's count
-                        const int* rj = rec + (size_t)tj * kBooRecord;
-                        const int4* r4 = (const int4*)rj;
-                        const int4 a = r4[0], b = r4[1];
-                        int u[PMC_BOO_TERMS] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, rj[8], 0, 0, 0, 0};
-                        if constexpr (L == 6) {
-                            u[9] = rj[9];
-                            u[10] = rj[10];
-                            u[11] = rj[11];
-                            u[12] = rj[12];
-                        }
-                        int* row = tab + i * NT;
-#pragma unroll
-                        for (int m = 0; m < NT; ++m)
-                            (void)__hip_atomic_fetch_add(row + m, u[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                    const int k = __popcll(im);
-                    n_pairs += (unsigned long long)k;
-                    mydeg += lane == i ? k : 0;
-                }
-            };
-            block(0, std::true_type{});
-            for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the table's atomics have landed
-            int na = 0;
-            if (own) {
-                const int* ri = rec + (size_t)(id0 + lane) * kBooRecord;
-                int32_t A[PMC_BOO_TERMS];
-#pragma unroll
-                for (int m = 0; m < PMC_BOO_TERMS; ++m) A[m] = m < NT ? tab[lane * NT + m] + ri[m] : 0;
-                na = (int)pmc_boo_avg_norm(A);
-                if (mydeg > 0)
-                    (void)__hip_atomic_fetch_add(&hist[pmc_boo_avg_bin((int64_t)na, mydeg, L, nq)], 1u, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            if (lane < nm) {
-                int* so = slot_out + (size_t)(id0 + lane) * kBooAvgSlot;
-                if constexpr (L == 4) *(int4*)so = make_int4(na, 0, own ? mydeg : 0, 0);
-                else so[1] = na;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_ and tab
+            return;
         }
-    }
+        // ---- ordered pairs (i, j): lane j holds staged partner j (blocks of 64), own particle
+        //      i (staged first, in slot order: lane i of block 0) broadcast by readlane; j == i skipped
+        const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+        const int ot = et_[lane];
+        int mydeg = 0;                                                 // lane i: deg(i)
+        auto block = [&](int jb, auto first_c) {
+            constexpr bool kFirst = decltype(first_c)::value;
+            const int j = jb + lane;
+            const bool vj = j < S;
+            const int jj = vj ? j : 0;
+            float xj = ox, yj = oy, zj = oz;
+            int tj = ot;
+            if constexpr (!kFirst) {
+                xj = ex_[jj];
+                yj = ey_[jj];
+                zj = ez_[jj];
+                tj = et_[jj];
+            }
+            const unsigned long long vm = __builtin_amdgcn_ballot_w64(vj);
+            for (int i = 0; i < n_own; ++i) {
+                const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+                const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+                const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+                const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
+                unsigned long long im = __builtin_amdgcn_ballot_w64(r2 <= rb2) & vm;
+                if constexpr (kFirst) im &= ~(1ull << i);
+                if (im == 0ull) continue;   // wave-uniform
+                if ((im >> lane) & 1ull) {
+                    // a hit lane holds a staged particle: tj is the id of a slot below its cell's count
+                    const int* rj = rec + (size_t)tj * kBooRecord;
+                    const int4* r4 = (const int4*)rj;
+                    const int4 a = r4[0], b = r4[1];
+                    int u[PMC_BOO_TERMS] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, rj[8], 0, 0, 0, 0};
+                    if constexpr (L == 6) {
+                        u[9] = rj[9];
+                        u[10] = rj[10];
+                        u[11] = rj[11];
+                        u[12] = rj[12];
+                    }
+                    int* row = tab + i * NT;
+#pragma unroll
+                    for (int m = 0; m < NT; ++m)
+                        (void)__hip_atomic_fetch_add(row + m, u[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                const int k = __popcll(im);
+                n_pairs += (unsigned long long)k;
+                mydeg += lane == i ? k : 0;
+            }
+        };
+        block(0, std::true_type{});
+        for (int jb = kWave; jb < S; jb += kWave) block(jb, std::false_type{});
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the table's atomics have landed
+        int na = 0;
+        if (own) {
+            const int* ri = rec + (size_t)(id0 + lane) * kBooRecord;
+            int32_t A[PMC_BOO_TERMS];
+#pragma unroll
+            for (int m = 0; m < PMC_BOO_TERMS; ++m) A[m] = m < NT ? tab[lane * NT + m] + ri[m] : 0;
+            na = (int)pmc_boo_avg_norm(A);
+            if (mydeg > 0)
+                (void)__hip_atomic_fetch_add(&hist[pmc_boo_avg_bin((int64_t)na, mydeg, L, nq)], 1u, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        if (lane < nm) {
+            int* so = slot_out + (size_t)(id0 + lane) * kBooAvgSlot;
+            if constexpr (L == 4) *(int4*)so = make_int4(na, 0, own ? mydeg : 0, 0);
+            else so[1] = na;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_ and tab
+    });
     // ---- flush into this wave's accumulator copy: the l = 4 pass counts the bonds and the particles
     unsigned long long* mine = acc + (size_t)(blockIdx.x & (kBooAvgCopies - 1)) * boo_avg_stride(nq, n2);
     if constexpr (L == 4) {
@@ -4027,12 +3767,9 @@ __global__ __launch_bounds__(256) void k_boo_joint(const int16_t* __restrict__ n
 // ------------------------------------------------------------------------------------------
 // test-particle energies (include/pmc_probe.h): per owned cell, kpc Widom insertions at Philox
 // positions (PMC_PROBE_INSERT) or the cell's own particles with their own slot skipped
-// (PMC_PROBE_REAL), each against the cell's 27-cell stencil.  k_pairobs' per-cell form: the same
-// stencil (pairobs_stencil), the same staging (rows of 8 slots, chunks for the fuller cells, own
-// cell first, the pmc_box_d2 filter -- exact for both modes: a probe lies inside the padded cell
-// box -- and the 27 * nmax LDS capacity), the same fixed grid of waves over runs of kPairObsRun
-// cells.  Per probe the lanes take the staged partners in blocks of 64 and keep an int64 sum of
-// the fixed-point terms outside the core; one DPP wave reduction, then the wave-uniform class
+// (PMC_PROBE_REAL), each against the cell's 27-cell stencil, staged by the cell walk (CellWalk; its
+// pmc_box_d2 filter is exact for both modes: a probe lies inside the padded cell box).  Per probe
+// the lanes take the staged partners in blocks of 64 and keep an int64 sum of the fixed-point terms outside the core; one DPP wave reduction, then the wave-uniform class
 // (below / bin / above) and lane 0 adds to the wave's private LDS histogram (u32 counts, int64
 // energy sums; a wave visits at most cells / 4096 + kPairObsRun cells of at most 64 probes, so a
 // count stays below 2^32).  One flush per wave with 64-bit global atomics into one of kProbeCopies
@@ -4081,10 +3818,6 @@ __global__ __launch_bounds__(kWave) void k_probe(DevGeom g, const float* __restr
                                                  int kpc, uint32_t sample, long long lo4, long long bw4, float inv_bw,
                                                  int nbins) {
     extern __shared__ __attribute__((aligned(16))) float psm[];
-    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
-    constexpr int CPP = kWave / HS;    // cells per staging pass
-    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
-    using DA = DiskAddr<OFF32>;
     const int lane = threadIdx.x;
     const int nm = g.nmax;
     const int cap = 27 * nm;
@@ -4094,8 +3827,6 @@ __global__ __launch_bounds__(kWave) void k_probe(DevGeom g, const float* __restr
     float* ez_ = ex_ + 2 * cap;
     int* inv_l = (int*)(ex_ + 3 * cap);            // list entry -> stencil lane (32 ints)
     unsigned* hist = (unsigned*)(inv_l + 32);      // nbins counters of this wave
-    const int p = lane % HS;
-    const int ee = lane / HS;
     const float rc2 = g.rc2;
     const bool real = mode == PMC_PROBE_REAL;
     unsigned long long n_probes = 0, n_over = 0, n_below = 0, n_above = 0, n_pairs = 0;   // wave-uniform
@@ -4103,160 +3834,60 @@ __global__ __launch_bounds__(kWave) void k_probe(DevGeom g, const float* __restr
         hist[b] = 0u;
         esum[b] = 0;
     }
-    if (lane < 32) inv_l[lane] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-
-    // rows of the cell in flight (k_pairobs' issue_rows): slots [0, HS) of its occupied stencil cells
-    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
-    bool vact[NPMAX];
-    int ncells = 0;
-    auto issue_rows = [&](const PairObsStencil& st) {
-        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
-        ncells = __popcll(mo);
-        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-        for (int q = 0; q < NPMAX; ++q) {
-            const int e = q * CPP + ee;
-            const int src = inv_l[e < ncells ? e : 0];
-            const int c_cnt = __shfl(st.cnt, src);
-            const int c_idx = __shfl(st.kc, src);
-            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
-            vact[q] = e < ncells && p < c_cnt;
-            vx[q] = vy[q] = vz[q] = 0.0f;
-            if (vact[q]) {
-                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
-                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
-                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
-                vy[q] = vy[q] + isy;
-                vz[q] = vz[q] + isz;
+    CellWalk<NSLOT, OFF32> walk(g, disk, ncnt, ex_, nullptr, inv_l);
+    walk.run(total_cells, [&](const WalkCell& cell, int S, int n_own) {
+        const int cx = __builtin_amdgcn_readfirstlane(cell.x), cy = __builtin_amdgcn_readfirstlane(cell.y);
+        const int czg = __builtin_amdgcn_readfirstlane(cell.zg);
+        // ---- the probes: lane i holds probe i (REAL: the own particles, staged first)
+        const int nprobe = real ? n_own : kpc;
+        n_probes += (unsigned long long)nprobe;
+        float px, py, pz;
+        if (real) {
+            px = ex_[lane];
+            py = ey_[lane];
+            pz = ez_[lane];
+        } else {
+            const uint32_t gid = (uint32_t)cx + (uint32_t)g.cps_x * ((uint32_t)cy + (uint32_t)g.cps_y * (uint32_t)czg);
+            const pmc_u32x4 wd = philox_rare((uint32_t)lane, gid, sample, PMC_TAG_PROBE, g);
+            px = pmc_probe_coord(wd.v[0], cx, g.w, g.Lx);
+            py = pmc_probe_coord(wd.v[1], cy, g.w, g.Ly);
+            pz = pmc_probe_coord(wd.v[2], czg, g.w, g.Lz);
+        }
+        for (int i = 0; i < nprobe; ++i) {
+            const float xi = as_f(__builtin_amdgcn_readlane(as_i(px), i));
+            const float yi = as_f(__builtin_amdgcn_readlane(as_i(py), i));
+            const float zi = as_f(__builtin_amdgcn_readlane(as_i(pz), i));
+            long long sum = 0;                 // per lane
+            unsigned long long hard = 0;       // lanes with a partner inside the core
+            for (int jb = 0; jb < S; jb += kWave) {
+                const int j = jb + lane;
+                const bool vj = j < S && !(real && j == i);
+                const int jj = j < S ? j : 0;
+                const float r2 = pmc_r2(xi - ex_[jj], yi - ey_[jj], zi - ez_[jj]);
+                const bool in = vj && r2 <= rc2;
+                const unsigned long long im = __builtin_amdgcn_ballot_w64(in);
+                if (im == 0ull) continue;
+                n_pairs += (unsigned long long)__popcll(im);
+                const bool core = in && r2 < PMC_PROBE_CORE_R2;
+                hard |= __builtin_amdgcn_ballot_w64(core);
+                const long long t = pmc_to_fixed_f32(pmc_lj4_from_r2(r2, rc2));
+                sum += in && !core ? t : 0ll;
+            }
+            if (hard) {
+                ++n_over;
+                continue;
+            }
+            const long long e4 = wave_sum_i64(sum);
+            const int cls = __builtin_amdgcn_readfirstlane(probe_bin_dev(e4, lo4, bw4, inv_bw, nbins));
+            if (cls < 0) ++n_below;
+            else if (cls >= nbins) ++n_above;
+            else if (lane == 0) {
+                hist[cls] += 1u;
+                esum[cls] += e4;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
-    };
-
-    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
-    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
-        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
-        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
-        issue_rows(cur);
-        PairObsStencil nxt = cur;
-        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
-        for (int c = 0; c < ncl; ++c) {
-            // ---- stage cell c (k_pairobs' staging): own particles first, then the filtered partners
-            float blo[3], bhi[3];
-            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
-            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
-            int S = 0;
-            auto put = [&](bool act, float ux, float uy, float uz) {
-                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
-                if (act) {
-                    const int dst = S + mbcnt64(am);
-                    ex_[dst] = ux;
-                    ey_[dst] = uy;
-                    ez_[dst] = uz;
-                }
-                S += __popcll(am);
-            };
-            auto chunks = [&](unsigned long long mg, bool filter) {
-                if constexpr (NSLOT > HS) {
-                    for (int s0 = HS; s0 < nm; s0 += HS) {
-                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
-                        while (ov) {
-                            int ks = 0, nc = 0;
-                            for (; nc < CPP && ov; ++nc) {
-                                const int kb = (int)__builtin_ctzll(ov);
-                                ov &= ov - 1ull;
-                                ks = ee == nc ? kb : ks;
-                            }
-                            const int c_cnt = __shfl(cur.cnt, ks);
-                            const int c_idx = __shfl(cur.kc, ks);
-                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
-                            const int ps = s0 + p;
-                            const bool act = ee < nc && ps < c_cnt;
-                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-                            if (act) {
-                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
-                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
-                                ux = ux + isx;
-                                uy = uy + isy;
-                                uz = uz + isz;
-                            }
-                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz);
-                        }
-                    }
-                }
-            };
-            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
-            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
-            const int cx = __builtin_amdgcn_readfirstlane(cur.x), cy = __builtin_amdgcn_readfirstlane(cur.y);
-            const int czg = __builtin_amdgcn_readfirstlane(cur.zg);
-            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0]);             // own slots [0, HS)
-            chunks(1ull, false);                                          // own slots [HS, n)
-#pragma unroll
-            for (int q = 0; q < NPMAX; ++q) {
-                const int e = q * CPP + ee;
-                if (q * CPP < ncells) put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q]);
-            }
-            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            // ---- the next cell's rows go out now and arrive while this cell's probes run
-            if (c + 1 < ncl) {
-                cur = nxt;
-                issue_rows(cur);
-                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
-            }
-            // ---- the probes: lane i holds probe i (REAL: the own particles, staged first)
-            const int nprobe = real ? n_own : kpc;
-            n_probes += (unsigned long long)nprobe;
-            float px, py, pz;
-            if (real) {
-                px = ex_[lane];
-                py = ey_[lane];
-                pz = ez_[lane];
-            } else {
-                const uint32_t gid = (uint32_t)cx + (uint32_t)g.cps_x * ((uint32_t)cy + (uint32_t)g.cps_y * (uint32_t)czg);
-                const pmc_u32x4 wd = philox_rare((uint32_t)lane, gid, sample, PMC_TAG_PROBE, g);
-                px = pmc_probe_coord(wd.v[0], cx, g.w, g.Lx);
-                py = pmc_probe_coord(wd.v[1], cy, g.w, g.Ly);
-                pz = pmc_probe_coord(wd.v[2], czg, g.w, g.Lz);
-            }
-            for (int i = 0; i < nprobe; ++i) {
-                const float xi = as_f(__builtin_amdgcn_readlane(as_i(px), i));
-                const float yi = as_f(__builtin_amdgcn_readlane(as_i(py), i));
-                const float zi = as_f(__builtin_amdgcn_readlane(as_i(pz), i));
-                long long sum = 0;                 // per lane
-                unsigned long long hard = 0;       // lanes with a partner inside the core
-                for (int jb = 0; jb < S; jb += kWave) {
-                    const int j = jb + lane;
-                    const bool vj = j < S && !(real && j == i);
-                    const int jj = j < S ? j : 0;
-                    const float r2 = pmc_r2(xi - ex_[jj], yi - ey_[jj], zi - ez_[jj]);
-                    const bool in = vj && r2 <= rc2;
-                    const unsigned long long im = __builtin_amdgcn_ballot_w64(in);
-                    if (im == 0ull) continue;
-                    n_pairs += (unsigned long long)__popcll(im);
-                    const bool core = in && r2 < PMC_PROBE_CORE_R2;
-                    hard |= __builtin_amdgcn_ballot_w64(core);
-                    const long long t = pmc_to_fixed_f32(pmc_lj4_from_r2(r2, rc2));
-                    sum += in && !core ? t : 0ll;
-                }
-                if (hard) {
-                    ++n_over;
-                    continue;
-                }
-                const long long e4 = wave_sum_i64(sum);
-                const int cls = __builtin_amdgcn_readfirstlane(probe_bin_dev(e4, lo4, bw4, inv_bw, nbins));
-                if (cls < 0) ++n_below;
-                else if (cls >= nbins) ++n_above;
-                else if (lane == 0) {
-                    hist[cls] += 1u;
-                    esum[cls] += e4;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
-        }
-    }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+    });
     // ---- flush: the wave's counters and its nonzero bins
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     unsigned long long* mine = acc + (size_t)(blockIdx.x & (kProbeCopies - 1)) * (size_t)(kProbeHead + 2 * nbins);
@@ -4275,8 +3906,8 @@ __global__ __launch_bounds__(kWave) void k_probe(DevGeom g, const float* __restr
 // ------------------------------------------------------------------------------------------
 // grand-canonical exchange moves (include/pmc_gc.h): one colour phase of insertions and deletions.
 // One wave per active cell at a time (a fixed grid of waves strides over the colour's cells): the
-// cell's stencil from pairobs_stencil, then k_probe's staging in two regions of LDS -- the own
-// cell's particles, unshifted and unfiltered, in [0, nmax), a region of their own that grows and
+// cell's stencil from pairobs_stencil, then a private variant of the cell walk's staging (DESIGN
+// 4.16) in two regions of LDS -- the own cell's particles, unshifted and unfiltered, in [0, nmax), a region of their own that grows and
 // shrinks with the accepted moves, and the neighbours' box-filtered partners from nmax on (capacity
 // 27 * nmax in all).  Lane k draws attempt k's Philox words, its insert position and its threshold
 // once; the kpc attempts then run as a sequential chain: the 64 lanes take the n own particles and
@@ -4335,8 +3966,8 @@ __global__ __launch_bounds__(kWave) void k_exchange(DevGeom g, float* disk, int1
             ey_[lane] = uy;
             ez_[lane] = uz;
         }
-        // neighbours (k_probe's staging over stencil cells 1..26): rows of slots [0, HS) of the occupied
-        // cells, then the fuller cells' slots [HS, n) in chunks, through the pmc_box_d2 filter, from nm on
+        // neighbours (CellWalk's row passes and chunks, over stencil cells 1..26 only): rows of slots
+        // [0, HS) of the occupied cells, then the fuller cells' slots [HS, n) in chunks, through the pmc_box_d2 filter, from nm on
         float blo[3], bhi[3];
         pmc_cell_box(cx, cy, czg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
         auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
@@ -4509,12 +4140,9 @@ __global__ __launch_bounds__(kWave) void k_exchange(DevGeom g, float* disk, int1
 // ------------------------------------------------------------------------------------------
 // axis profiles (include/pmc_profile.h): per bin along one box axis, the particle count and the
 // three diagonal pair-virial components over ORDERED pairs, each pair in its own particle's bin.
-// k_pairobs' per-cell form: the same stencil (pairobs_stencil), the same staging (rows of 8 slots,
-// the next cell's while this cell's pairs run, chunks for the fuller cells, own cell first, the
-// pmc_box_d2 filter, 27 * nmax LDS capacity), the same fixed grid of waves over runs of kPairObsRun
-// cells.  The pair loop is the other way round: the OWN particle is the outer loop (readlane), the
-// lanes take its staged partners in blocks of 64 (blocks 0 and 1 from registers, further ones from
-// LDS), every in-cutoff lane evaluates v and the three t_d and adds their fixed-point values to
+// The cell walk (CellWalk) stages each cell.  The pair loop is the other way round from
+// k_pairobs': the OWN particle is the outer loop (readlane), the lanes take its staged partners
+// in blocks of 64 (blocks 0 and 1 from registers, further ones from LDS), every in-cutoff lane evaluates v and the three t_d and adds their fixed-point values to
 // three per-lane int64 sums; one DPP wave reduction per component (wave_sum_i64) gives the
 // particle's sums, which lane i keeps.  After the cell, lanes < n_own add their particle's count and
 // sums to the wave's WINDOW in LDS: kProfWin consecutive bins from wlo (u32 counts, int64 sums,
@@ -4533,10 +4161,6 @@ __global__ __launch_bounds__(kWave) void k_profile(DevGeom g, const float* __res
                                                    unsigned long long* __restrict__ acc, uint32_t total_cells,
                                                    int axis, int nbins, int cps_a, float scale) {
     extern __shared__ __attribute__((aligned(16))) float psm[];
-    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
-    constexpr int CPP = kWave / HS;    // cells per staging pass
-    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
-    using DA = DiskAddr<OFF32>;
     const int lane = threadIdx.x;
     const int nm = g.nmax;
     const int cap = 27 * nm;
@@ -4546,8 +4170,6 @@ __global__ __launch_bounds__(kWave) void k_profile(DevGeom g, const float* __res
     float* ex_ = (float*)(inv_l + 32);
     float* ey_ = ex_ + cap;
     float* ez_ = ex_ + 2 * cap;
-    const int p = lane % HS;
-    const int ee = lane / HS;
     const float rc2 = g.rc2;
     long long sum = 0;                             // per lane: the virial total
     unsigned long long n_pairs = 0, n_part = 0;    // wave-uniform
@@ -4555,8 +4177,7 @@ __global__ __launch_bounds__(kWave) void k_profile(DevGeom g, const float* __res
         wcnt[b] = 0u;
         wvir[b] = wvir[kProfWin + b] = wvir[2 * kProfWin + b] = 0ull;
     }
-    if (lane < 32) inv_l[lane] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    CellWalk<NSLOT, OFF32> walk(g, disk, ncnt, ex_, nullptr, inv_l);
     unsigned long long* mine = acc + (size_t)(blockIdx.x & (kProfCopies - 1)) * ((size_t)kProfHead + 4 * (size_t)nbins);
     unsigned long long* gcnt = mine + kProfHead;
     unsigned long long* gvir = gcnt + nbins;       // [3][nbins]
@@ -4580,182 +4201,82 @@ __global__ __launch_bounds__(kWave) void k_profile(DevGeom g, const float* __res
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     };
 
-    // rows of the cell in flight (k_pairobs' issue_rows): slots [0, HS) of its occupied stencil cells
-    // (own cell: entry 0 when occupied), in registers
-    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
-    bool vact[NPMAX];
-    int ncells = 0;
-    auto issue_rows = [&](const PairObsStencil& st) {
-        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
-        ncells = __popcll(mo);
-        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-        for (int q = 0; q < NPMAX; ++q) {
-            const int e = q * CPP + ee;
-            const int src = inv_l[e < ncells ? e : 0];
-            const int c_cnt = __shfl(st.cnt, src);
-            const int c_idx = __shfl(st.kc, src);
-            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
-            vact[q] = e < ncells && p < c_cnt;
-            vx[q] = vy[q] = vz[q] = 0.0f;
-            if (vact[q]) {
-                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
-                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
-                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
-                vy[q] = vy[q] + isy;
-                vz[q] = vz[q] + isz;
+    walk.run(total_cells, [&](const WalkCell& cell, int S, int n_own) {
+        const int ca = axis == 0 ? cell.x : (axis == 1 ? cell.y : cell.zg);   // the cell along the axis
+        n_part += (unsigned long long)n_own;
+        if (n_own == 0) return;
+        // ---- the window holds this cell's bins, or is flushed and re-anchored at them
+        {
+            const int lo_c = (int)(((uint32_t)ca * (uint32_t)nbins) / (uint32_t)cps_a) - 1;
+            const int hi_c = (int)(((uint32_t)(ca + 1) * (uint32_t)nbins) / (uint32_t)cps_a) + 1;
+            if (lo_c < wlo || hi_c >= wlo + kProfWin) {
+                flush_window();
+                wlo = lo_c;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
-    };
-
-    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
-    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
-        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
-        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
-        issue_rows(cur);
-        PairObsStencil nxt = cur;
-        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
-        for (int c = 0; c < ncl; ++c) {
-            // ---- stage cell c (k_pairobs' staging): own particles first, then the filtered partners
-            float blo[3], bhi[3];
-            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
-            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
-            const int ca = axis == 0 ? cur.x : (axis == 1 ? cur.y : cur.zg);   // the cell along the axis
-            int S = 0;
-            auto put = [&](bool act, float ux, float uy, float uz) {
-                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
-                if (act) {
-                    const int dst = S + mbcnt64(am);
-                    ex_[dst] = ux;
-                    ey_[dst] = uy;
-                    ez_[dst] = uz;
-                }
-                S += __popcll(am);
-            };
-            // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles
-            auto chunks = [&](unsigned long long mg, bool filter) {
-                if constexpr (NSLOT > HS) {
-                    for (int s0 = HS; s0 < nm; s0 += HS) {
-                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
-                        while (ov) {
-                            int ks = 0, nc = 0;
-                            for (; nc < CPP && ov; ++nc) {
-                                const int kb = (int)__builtin_ctzll(ov);
-                                ov &= ov - 1ull;
-                                ks = ee == nc ? kb : ks;
-                            }
-                            const int c_cnt = __shfl(cur.cnt, ks);
-                            const int c_idx = __shfl(cur.kc, ks);
-                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
-                            const int ps = s0 + p;
-                            const bool act = ee < nc && ps < c_cnt;
-                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-                            if (act) {
-                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
-                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
-                                ux = ux + isx;
-                                uy = uy + isy;
-                                uz = uz + isz;
-                            }
-                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz);
-                        }
-                    }
+        // ---- ordered pairs (i, j): own particle i (staged first: lane i of block 0) by readlane,
+        //      lane j holds staged partner j of the block; j == i skipped
+        const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+        const int j1 = kWave + lane < S ? kWave + lane : 0;
+        const float px = ex_[j1], py = ey_[j1], pz = ez_[j1];         // block 1
+        long long mx = 0, my = 0, mz = 0;                             // lane i: particle i's sums
+        for (int i = 0; i < n_own; ++i) {
+            const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+            const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+            const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+            long long ax = 0, ay = 0, az = 0;
+            auto block = [&](int jb, float xj, float yj, float zj, bool self) {
+                const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
+                const float r2 = pmc_r2(dx, dy, dz);
+                const bool in = r2 <= rc2 && jb + lane < S && !self;
+                const unsigned long long im = __builtin_amdgcn_ballot_w64(in);
+                if (im == 0ull) return;
+                n_pairs += (unsigned long long)__popcll(im);
+                if (in) {
+                    const float v = pmc_virial_term(r2);
+                    const float inv = pmc_recip(__builtin_fmaxf(r2, PMC_R2_MIN));
+                    sum += pmc_to_fixed_f32(v);
+                    ax += pmc_to_fixed_f32(pmc_profile_term_inv(v, dx, inv));
+                    ay += pmc_to_fixed_f32(pmc_profile_term_inv(v, dy, inv));
+                    az += pmc_to_fixed_f32(pmc_profile_term_inv(v, dz, inv));
                 }
             };
-            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
-            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
-            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0]);             // own slots [0, HS)
-            chunks(1ull, false);                                          // own slots [HS, n)
-#pragma unroll
-            for (int q = 0; q < NPMAX; ++q) {
-                const int e = q * CPP + ee;
-                if (q * CPP < ncells) put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q]);
+            block(0, ox, oy, oz, lane == i);
+            if (S > kWave) block(kWave, px, py, pz, false);
+            for (int jb = 2 * kWave; jb < S; jb += kWave) {
+                const int jj = jb + lane < S ? jb + lane : 0;
+                block(jb, ex_[jj], ey_[jj], ez_[jj], false);
             }
-            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            // ---- the next cell's rows go out now and arrive while this cell's pairs run
-            if (c + 1 < ncl) {
-                cur = nxt;
-                issue_rows(cur);
-                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
+            const long long tx = wave_sum_i64(ax), ty = wave_sum_i64(ay), tz = wave_sum_i64(az);
+            if (lane == i) {
+                mx = tx;
+                my = ty;
+                mz = tz;
             }
-            n_part += (unsigned long long)n_own;
-            if (n_own == 0) continue;
-            // ---- the window holds this cell's bins, or is flushed and re-anchored at them
-            {
-                const int lo_c = (int)(((uint32_t)ca * (uint32_t)nbins) / (uint32_t)cps_a) - 1;
-                const int hi_c = (int)(((uint32_t)(ca + 1) * (uint32_t)nbins) / (uint32_t)cps_a) + 1;
-                if (lo_c < wlo || hi_c >= wlo + kProfWin) {
-                    flush_window();
-                    wlo = lo_c;
-                }
-            }
-            // ---- ordered pairs (i, j): own particle i (staged first: lane i of block 0) by readlane,
-            //      lane j holds staged partner j of the block; j == i skipped
-            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
-            const int j1 = kWave + lane < S ? kWave + lane : 0;
-            const float px = ex_[j1], py = ey_[j1], pz = ez_[j1];         // block 1
-            long long mx = 0, my = 0, mz = 0;                             // lane i: particle i's sums
-            for (int i = 0; i < n_own; ++i) {
-                const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
-                const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
-                const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
-                long long ax = 0, ay = 0, az = 0;
-                auto block = [&](int jb, float xj, float yj, float zj, bool self) {
-                    const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
-                    const float r2 = pmc_r2(dx, dy, dz);
-                    const bool in = r2 <= rc2 && jb + lane < S && !self;
-                    const unsigned long long im = __builtin_amdgcn_ballot_w64(in);
-                    if (im == 0ull) return;
-                    n_pairs += (unsigned long long)__popcll(im);
-                    if (in) {
-                        const float v = pmc_virial_term(r2);
-                        const float inv = pmc_recip(__builtin_fmaxf(r2, PMC_R2_MIN));
-                        sum += pmc_to_fixed_f32(v);
-                        ax += pmc_to_fixed_f32(pmc_profile_term_inv(v, dx, inv));
-                        ay += pmc_to_fixed_f32(pmc_profile_term_inv(v, dy, inv));
-                        az += pmc_to_fixed_f32(pmc_profile_term_inv(v, dz, inv));
-                    }
-                };
-                block(0, ox, oy, oz, lane == i);
-                if (S > kWave) block(kWave, px, py, pz, false);
-                for (int jb = 2 * kWave; jb < S; jb += kWave) {
-                    const int jj = jb + lane < S ? jb + lane : 0;
-                    block(jb, ex_[jj], ey_[jj], ez_[jj], false);
-                }
-                const long long tx = wave_sum_i64(ax), ty = wave_sum_i64(ay), tz = wave_sum_i64(az);
-                if (lane == i) {
-                    mx = tx;
-                    my = ty;
-                    mz = tz;
-                }
-            }
-            // ---- lanes < n_own: the particle's bin, its count and sums into the window or, outside
-            //      it, the global accumulator
-            if (lane < n_own) {
-                const float oa = axis == 0 ? ox : (axis == 1 ? oy : oz);
-                const int b = (int)pmc_profile_bin(pmc_sk_word(oa, scale), nbins);
-                const int e = b - wlo;
-                if (e >= 0 && e < kProfWin) {
-                    (void)__hip_atomic_fetch_add(&wcnt[e], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    (void)__hip_atomic_fetch_add(&wvir[e], (unsigned long long)mx, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
-                    (void)__hip_atomic_fetch_add(&wvir[kProfWin + e], (unsigned long long)my, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
-                    (void)__hip_atomic_fetch_add(&wvir[2 * kProfWin + e], (unsigned long long)mz, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
-                } else {
-                    atomicAdd(&gcnt[b], 1ull);
-                    if (mx) atomicAdd(&gvir[b], (unsigned long long)mx);
-                    if (my) atomicAdd(&gvir[(size_t)nbins + b], (unsigned long long)my);
-                    if (mz) atomicAdd(&gvir[2 * (size_t)nbins + b], (unsigned long long)mz);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
         }
-    }
+        // ---- lanes < n_own: the particle's bin, its count and sums into the window or, outside
+        //      it, the global accumulator
+        if (lane < n_own) {
+            const float oa = axis == 0 ? ox : (axis == 1 ? oy : oz);
+            const int b = (int)pmc_profile_bin(pmc_sk_word(oa, scale), nbins);
+            const int e = b - wlo;
+            if (e >= 0 && e < kProfWin) {
+                (void)__hip_atomic_fetch_add(&wcnt[e], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_add(&wvir[e], (unsigned long long)mx, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_add(&wvir[kProfWin + e], (unsigned long long)my, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_add(&wvir[2 * kProfWin + e], (unsigned long long)mz, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+            } else {
+                atomicAdd(&gcnt[b], 1ull);
+                if (mx) atomicAdd(&gvir[b], (unsigned long long)mx);
+                if (my) atomicAdd(&gvir[(size_t)nbins + b], (unsigned long long)my);
+                if (mz) atomicAdd(&gvir[2 * (size_t)nbins + b], (unsigned long long)mz);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+    });
     // ---- flush: the window, then the wave sums (int64, exact in any order)
     flush_window();
 #pragma unroll
@@ -4767,8 +4288,8 @@ __global__ __launch_bounds__(kWave) void k_profile(DevGeom g, const float* __res
 // ------------------------------------------------------------------------------------------
 // axis profiles on the Irving-Kirkwood contour (include/pmc_profile_ik.h): k_profile's counts and
 // totals, but every ordered pair's three fixed-point terms are SPREAD over the bins its segment
-// crosses along the axis.  k_profile's stencil, staging (with a fourth staged value: the t word of
-// the partner's STORED axis coordinate, taken before the image shift is added), filter, grid and
+// crosses along the axis.  The cell walk (CellWalk, with a word payload: the t word of
+// the partner's STORED axis coordinate, taken before the image shift is added) and k_profile's
 // pair loop (own particle i by readlane, lanes = staged partners).  Per in-cutoff lane:
 //   - the whole pair in i's own bin (S = 0, or a segment inside that bin): three per-lane int64
 //     sums, one wave reduction per particle, no atomics -- k_profile's path;
@@ -4795,11 +4316,7 @@ __global__ __launch_bounds__(kWave) void k_profile_ik(DevGeom g, const float* __
                                                       unsigned long long* __restrict__ acc, uint32_t total_cells,
                                                       int axis, int nbins, int cps_a, float scale) {
     extern __shared__ __attribute__((aligned(16))) float psm[];
-    constexpr int HS = 8;              // staging lanes per cell and pass (slots [s0, s0 + 8))
-    constexpr int CPP = kWave / HS;    // cells per staging pass
-    constexpr int NPMAX = 4;           // main passes: 32 list entries >= 27 stencil cells
     constexpr int W = kProfIkWin;
-    using DA = DiskAddr<OFF32>;
     const int lane = threadIdx.x;
     const int nm = g.nmax;
     const int cap = 27 * nm;
@@ -4810,8 +4327,6 @@ __global__ __launch_bounds__(kWave) void k_profile_ik(DevGeom g, const float* __
     float* ey_ = ex_ + cap;
     float* ez_ = ex_ + 2 * cap;
     uint32_t* ew_ = (uint32_t*)(ex_ + 3 * cap);                 // t word of the stored axis coordinate
-    const int p = lane % HS;
-    const int ee = lane / HS;
     const float rc2 = g.rc2;
     const double inv_nb = 1.0 / (double)nbins;
     const int wn = nbins < W ? nbins : W;          // window entries in use
@@ -4821,8 +4336,11 @@ __global__ __launch_bounds__(kWave) void k_profile_ik(DevGeom g, const float* __
         wcnt[b] = 0u;
         wvir[b] = wvir[W + b] = wvir[2 * W + b] = 0ull;
     }
-    if (lane < 32) inv_l[lane] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    // the fourth staged value: the t word of the partner's STORED axis coordinate
+    const auto word = word_payload([&](float x, float y, float z) {
+        return pmc_ik_word(pmc_sk_word(axis == 0 ? x : (axis == 1 ? y : z), scale));
+    });
+    CellWalk<NSLOT, OFF32, decltype(word)> walk(g, disk, ncnt, ex_, ew_, inv_l, word);
     unsigned long long* mine = acc + (size_t)(blockIdx.x & (kProfCopies - 1)) * ((size_t)kProfHead + 4 * (size_t)nbins);
     unsigned long long* gcnt = mine + kProfHead;
     unsigned long long* gvir = gcnt + nbins;       // [3][nbins]
@@ -4863,218 +4381,111 @@ __global__ __launch_bounds__(kWave) void k_profile_ik(DevGeom g, const float* __
         }
     };
 
-    // rows of the cell in flight (k_pairobs' issue_rows): slots [0, HS) of its occupied stencil cells
-    // (own cell: entry 0 when occupied), in registers; vw: the t word of the stored axis coordinate
-    float vx[NPMAX], vy[NPMAX], vz[NPMAX];
-    uint32_t vw[NPMAX];
-    bool vact[NPMAX];
-    int ncells = 0;
-    auto issue_rows = [&](const PairObsStencil& st) {
-        const unsigned long long mo = __builtin_amdgcn_ballot_w64(st.cnt > 0);
-        ncells = __popcll(mo);
-        if (st.cnt > 0) inv_l[mbcnt64(mo)] = lane;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-        for (int q = 0; q < NPMAX; ++q) {
-            const int e = q * CPP + ee;
-            const int src = inv_l[e < ncells ? e : 0];
-            const int c_cnt = __shfl(st.cnt, src);
-            const int c_idx = __shfl(st.kc, src);
-            const float isx = __shfl(st.sx, src), isy = __shfl(st.sy, src), isz = __shfl(st.sz, src);
-            vact[q] = e < ncells && p < c_cnt;
-            vx[q] = vy[q] = vz[q] = 0.0f;
-            vw[q] = 0u;
-            if (vact[q]) {
-                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)p * lay_slot()) * DA::kUnit;
-                DA::ld3(disk, off, lay_dim(nm), vx[q], vy[q], vz[q]);
-                vw[q] = pmc_ik_word(pmc_sk_word(axis == 0 ? vx[q] : (axis == 1 ? vy[q] : vz[q]), scale));
-                vx[q] = vx[q] + isx;   // (+0 for the cells that are not wrapped)
-                vy[q] = vy[q] + isy;
-                vz[q] = vz[q] + isz;
+    walk.run(total_cells, [&](const WalkCell& cell, int S, int n_own) {
+        const int ca = axis == 0 ? cell.x : (axis == 1 ? cell.y : cell.zg);   // the cell along the axis
+        n_part += (unsigned long long)n_own;
+        if (n_own == 0) return;
+        // ---- the window holds this cell's three-cell span, or is flushed and re-anchored at it
+        //      (a box of at most W bins is in the window whole: never re-anchored)
+        if (nbins > W) {
+            const int lo_c = (int)(((uint32_t)(ca - 1 + cps_a) * (uint32_t)nbins) / (uint32_t)cps_a) - nbins - 1;
+            const int hi_c = (int)(((uint32_t)(ca + 2) * (uint32_t)nbins) / (uint32_t)cps_a) + 1;
+            if (lo_c < wraw || hi_c >= wraw + W) {
+                flush_window();
+                wraw = lo_c;
+                wmod = lo_c < 0 ? lo_c + nbins : lo_c;   // lo_c >= -(nbins / cps_a + 2) > -nbins here
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // inv_l is rewritten by the next call
-    };
-
-    const uint32_t stride = gridDim.x * (uint32_t)kPairObsRun;
-    for (uint32_t base = blockIdx.x * (uint32_t)kPairObsRun; base < total_cells; base += stride) {
-        const int ncl = (int)(total_cells - base < (uint32_t)kPairObsRun ? total_cells - base : (uint32_t)kPairObsRun);
-        PairObsStencil cur = pairobs_stencil(g, ncnt, base);
-        issue_rows(cur);
-        PairObsStencil nxt = cur;
-        if (ncl > 1) nxt = pairobs_stencil(g, ncnt, base + 1u);
-        for (int c = 0; c < ncl; ++c) {
-            // ---- stage cell c (k_pairobs' staging): own particles first, then the filtered partners
-            float blo[3], bhi[3];
-            pmc_cell_box(cur.x, cur.y, cur.zg, g.w, g.Lx, g.Ly, g.Lz, blo, bhi);
-            auto near = [&](float ux, float uy, float uz) { return pmc_box_d2(ux, uy, uz, blo, bhi) <= g.rc2f; };
-            const int ca = axis == 0 ? cur.x : (axis == 1 ? cur.y : cur.zg);   // the cell along the axis
-            int S = 0;
-            auto put = [&](bool act, float ux, float uy, float uz, uint32_t uw) {
-                const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
-                if (act) {
-                    const int dst = S + mbcnt64(am);
-                    ex_[dst] = ux;
-                    ey_[dst] = uy;
-                    ez_[dst] = uz;
-                    ew_[dst] = uw;
-                }
-                S += __popcll(am);
-            };
-            // slots [s0, s0 + HS) of the stencil cells in mask mg that hold more than s0 particles
-            auto chunks = [&](unsigned long long mg, bool filter) {
-                if constexpr (NSLOT > HS) {
-                    for (int s0 = HS; s0 < nm; s0 += HS) {
-                        unsigned long long ov = __builtin_amdgcn_ballot_w64(((mg >> lane) & 1ull) && cur.cnt > s0);
-                        while (ov) {
-                            int ks = 0, nc = 0;
-                            for (; nc < CPP && ov; ++nc) {
-                                const int kb = (int)__builtin_ctzll(ov);
-                                ov &= ov - 1ull;
-                                ks = ee == nc ? kb : ks;
-                            }
-                            const int c_cnt = __shfl(cur.cnt, ks);
-                            const int c_idx = __shfl(cur.kc, ks);
-                            const float isx = __shfl(cur.sx, ks), isy = __shfl(cur.sy, ks), isz = __shfl(cur.sz, ks);
-                            const int ps = s0 + p;
-                            const bool act = ee < nc && ps < c_cnt;
-                            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-                            uint32_t uw = 0u;
-                            if (act) {
-                                const uint32_t off = ((uint32_t)c_idx * (uint32_t)(3 * nm) + (uint32_t)ps * lay_slot()) * DA::kUnit;
-                                DA::ld3(disk, off, lay_dim(nm), ux, uy, uz);
-                                uw = pmc_ik_word(pmc_sk_word(axis == 0 ? ux : (axis == 1 ? uy : uz), scale));
-                                ux = ux + isx;
-                                uy = uy + isy;
-                                uz = uz + isz;
-                            }
-                            put(act && (!filter || near(ux, uy, uz)), ux, uy, uz, uw);
-                        }
-                    }
-                }
-            };
-            const int n_own = __builtin_amdgcn_readfirstlane(cur.cnt);   // lane 0 = own cell
-            const int e_own = n_own > 0 ? 1 : 0;                          // list entries of the own cell
-            put(vact[0] && ee < e_own, vx[0], vy[0], vz[0], vw[0]);      // own slots [0, HS)
-            chunks(1ull, false);                                          // own slots [HS, n)
-#pragma unroll
-            for (int q = 0; q < NPMAX; ++q) {
-                const int e = q * CPP + ee;
-                if (q * CPP < ncells)
-                    put(vact[q] && e >= e_own && near(vx[q], vy[q], vz[q]), vx[q], vy[q], vz[q], vw[q]);
-            }
-            chunks(0x7FFFFFEull, true);                                   // stencil cells 1..26
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            // ---- the next cell's rows go out now and arrive while this cell's pairs run
-            if (c + 1 < ncl) {
-                cur = nxt;
-                issue_rows(cur);
-                if (c + 2 < ncl) nxt = pairobs_stencil(g, ncnt, base + (uint32_t)(c + 2));
-            }
-            n_part += (unsigned long long)n_own;
-            if (n_own == 0) continue;
-            // ---- the window holds this cell's three-cell span, or is flushed and re-anchored at it
-            //      (a box of at most W bins is in the window whole: never re-anchored)
-            if (nbins > W) {
-                const int lo_c = (int)(((uint32_t)(ca - 1 + cps_a) * (uint32_t)nbins) / (uint32_t)cps_a) - nbins - 1;
-                const int hi_c = (int)(((uint32_t)(ca + 2) * (uint32_t)nbins) / (uint32_t)cps_a) + 1;
-                if (lo_c < wraw || hi_c >= wraw + W) {
-                    flush_window();
-                    wraw = lo_c;
-                    wmod = lo_c < 0 ? lo_c + nbins : lo_c;   // lo_c >= -(nbins / cps_a + 2) > -nbins here
-                }
-            }
-            // ---- ordered pairs (i, j): own particle i (staged first: lane i of block 0) by readlane,
-            //      lane j holds staged partner j of the block; j == i skipped
-            const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
-            const uint32_t ow = ew_[lane];
-            const int j1 = kWave + lane < S ? kWave + lane : 0;
-            const float px = ex_[j1], py = ey_[j1], pz = ez_[j1];         // block 1
-            const uint32_t pw = ew_[j1];
-            long long mx = 0, my = 0, mz = 0;                             // lane i: particle i's own-bin sums
-            for (int i = 0; i < n_own; ++i) {
-                const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
-                const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
-                const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
-                const uint32_t ti = (uint32_t)__builtin_amdgcn_readlane((int)ow, i);
-                const int bi = (int)pmc_profile_bin(ti - 0x80000000u, nbins);   // i's bin (wave-uniform)
-                long long ax = 0, ay = 0, az = 0;
-                auto block = [&](int jb, float xj, float yj, float zj, uint32_t tj, bool self) {
-                    const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
-                    const float r2 = pmc_r2(dx, dy, dz);
-                    const bool in = r2 <= rc2 && jb + lane < S && !self;
-                    const unsigned long long im = __builtin_amdgcn_ballot_w64(in);
-                    if (im == 0ull) return;
-                    n_pairs += (unsigned long long)__popcll(im);
-                    if (in) {
-                        const float v = pmc_virial_term(r2);
-                        const float inv = pmc_recip(__builtin_fmaxf(r2, PMC_R2_MIN));
-                        sum += pmc_to_fixed_f32(v);
-                        const long long Tx = pmc_to_fixed_f32(pmc_profile_term_inv(v, dx, inv));
-                        const long long Ty = pmc_to_fixed_f32(pmc_profile_term_inv(v, dy, inv));
-                        const long long Tz = pmc_to_fixed_f32(pmc_profile_term_inv(v, dz, inv));
-                        const int32_t s = pmc_ik_sep(ti, tj);
-                        const long long Sg = pmc_ik_len(s);
-                        const long long lo = pmc_ik_lo(ti, s);
-                        const long long k0 = pmc_ik_bin(lo, nbins);
-                        const long long k1 = Sg == 0 ? k0 : pmc_ik_bin(lo + Sg - 1, nbins);
-                        if (k0 == k1) {   // the whole pair in one bin (S = 0: lo = t_i + 2^32, i's bin)
-                            const int b = (int)pmc_ik_wrap(k0, nbins);
-                            if (b == bi) {
-                                ax += Tx;
-                                ay += Ty;
-                                az += Tz;
-                            } else {
-                                deposit(b, Tx, Ty, Tz);
-                            }
+        // ---- ordered pairs (i, j): own particle i (staged first: lane i of block 0) by readlane,
+        //      lane j holds staged partner j of the block; j == i skipped
+        const float ox = ex_[lane], oy = ey_[lane], oz = ez_[lane];   // block 0 (own at lanes < n_own)
+        const uint32_t ow = ew_[lane];
+        const int j1 = kWave + lane < S ? kWave + lane : 0;
+        const float px = ex_[j1], py = ey_[j1], pz = ez_[j1];         // block 1
+        const uint32_t pw = ew_[j1];
+        long long mx = 0, my = 0, mz = 0;                             // lane i: particle i's own-bin sums
+        for (int i = 0; i < n_own; ++i) {
+            const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+            const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+            const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+            const uint32_t ti = (uint32_t)__builtin_amdgcn_readlane((int)ow, i);
+            const int bi = (int)pmc_profile_bin(ti - 0x80000000u, nbins);   // i's bin (wave-uniform)
+            long long ax = 0, ay = 0, az = 0;
+            auto block = [&](int jb, float xj, float yj, float zj, uint32_t tj, bool self) {
+                const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
+                const float r2 = pmc_r2(dx, dy, dz);
+                const bool in = r2 <= rc2 && jb + lane < S && !self;
+                const unsigned long long im = __builtin_amdgcn_ballot_w64(in);
+                if (im == 0ull) return;
+                n_pairs += (unsigned long long)__popcll(im);
+                if (in) {
+                    const float v = pmc_virial_term(r2);
+                    const float inv = pmc_recip(__builtin_fmaxf(r2, PMC_R2_MIN));
+                    sum += pmc_to_fixed_f32(v);
+                    const long long Tx = pmc_to_fixed_f32(pmc_profile_term_inv(v, dx, inv));
+                    const long long Ty = pmc_to_fixed_f32(pmc_profile_term_inv(v, dy, inv));
+                    const long long Tz = pmc_to_fixed_f32(pmc_profile_term_inv(v, dz, inv));
+                    const int32_t s = pmc_ik_sep(ti, tj);
+                    const long long Sg = pmc_ik_len(s);
+                    const long long lo = pmc_ik_lo(ti, s);
+                    const long long k0 = pmc_ik_bin(lo, nbins);
+                    const long long k1 = Sg == 0 ? k0 : pmc_ik_bin(lo + Sg - 1, nbins);
+                    if (k0 == k1) {   // the whole pair in one bin (S = 0: lo = t_i + 2^32, i's bin)
+                        const int b = (int)pmc_ik_wrap(k0, nbins);
+                        if (b == bi) {
+                            ax += Tx;
+                            ay += Ty;
+                            az += Tz;
                         } else {
-                            const double inv_s = 1.0 / (double)Sg;
-                            int64_t qx, rx, qy, ry, qz, rz;
-                            pmc_ik_split(Tx, Sg, inv_s, &qx, &rx);
-                            pmc_ik_split(Ty, Sg, inv_s, &qy, &ry);
-                            pmc_ik_split(Tz, Sg, inv_s, &qz, &rz);
-                            long long cx = 0, cy = 0, cz = 0;   // C_d(m_{k0}) = 0: B_{k0} <= lo
-                            int b = (int)pmc_ik_wrap(k0, nbins);
-                            for (long long k = k0; k <= k1; ++k) {
-                                const long long m = pmc_ik_clamp(pmc_ik_boundary(k + 1, nbins, inv_nb) - lo, Sg);
-                                const long long nx = pmc_ik_cum(Tx, qx, rx, m, Sg, inv_s);
-                                const long long ny = pmc_ik_cum(Ty, qy, ry, m, Sg, inv_s);
-                                const long long nz = pmc_ik_cum(Tz, qz, rz, m, Sg, inv_s);
-                                deposit(b, nx - cx, ny - cy, nz - cz);
-                                cx = nx;
-                                cy = ny;
-                                cz = nz;
-                                b = b + 1 == nbins ? 0 : b + 1;
-                            }
+                            deposit(b, Tx, Ty, Tz);
+                        }
+                    } else {
+                        const double inv_s = 1.0 / (double)Sg;
+                        int64_t qx, rx, qy, ry, qz, rz;
+                        pmc_ik_split(Tx, Sg, inv_s, &qx, &rx);
+                        pmc_ik_split(Ty, Sg, inv_s, &qy, &ry);
+                        pmc_ik_split(Tz, Sg, inv_s, &qz, &rz);
+                        long long cx = 0, cy = 0, cz = 0;   // C_d(m_{k0}) = 0: B_{k0} <= lo
+                        int b = (int)pmc_ik_wrap(k0, nbins);
+                        for (long long k = k0; k <= k1; ++k) {
+                            const long long m = pmc_ik_clamp(pmc_ik_boundary(k + 1, nbins, inv_nb) - lo, Sg);
+                            const long long nx = pmc_ik_cum(Tx, qx, rx, m, Sg, inv_s);
+                            const long long ny = pmc_ik_cum(Ty, qy, ry, m, Sg, inv_s);
+                            const long long nz = pmc_ik_cum(Tz, qz, rz, m, Sg, inv_s);
+                            deposit(b, nx - cx, ny - cy, nz - cz);
+                            cx = nx;
+                            cy = ny;
+                            cz = nz;
+                            b = b + 1 == nbins ? 0 : b + 1;
                         }
                     }
-                };
-                block(0, ox, oy, oz, ow, lane == i);
-                if (S > kWave) block(kWave, px, py, pz, pw, false);
-                for (int jb = 2 * kWave; jb < S; jb += kWave) {
-                    const int jj = jb + lane < S ? jb + lane : 0;
-                    block(jb, ex_[jj], ey_[jj], ez_[jj], ew_[jj], false);
                 }
-                const long long tx = wave_sum_i64(ax), ty = wave_sum_i64(ay), tz = wave_sum_i64(az);
-                if (lane == i) {
-                    mx = tx;
-                    my = ty;
-                    mz = tz;
-                }
+            };
+            block(0, ox, oy, oz, ow, lane == i);
+            if (S > kWave) block(kWave, px, py, pz, pw, false);
+            for (int jb = 2 * kWave; jb < S; jb += kWave) {
+                const int jj = jb + lane < S ? jb + lane : 0;
+                block(jb, ex_[jj], ey_[jj], ez_[jj], ew_[jj], false);
             }
-            // ---- lanes < n_own: the particle's count and own-bin sums into the window or, outside it,
-            //      the global accumulator
-            if (lane < n_own) {
-                const int b = (int)pmc_profile_bin(ow - 0x80000000u, nbins);
-                int e = b - wmod;
-                e = e < 0 ? e + nbins : e;
-                if (e < wn) (void)__hip_atomic_fetch_add(&wcnt[e], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                else atomicAdd(&gcnt[b], 1ull);
-                deposit(b, mx, my, mz);
+            const long long tx = wave_sum_i64(ax), ty = wave_sum_i64(ay), tz = wave_sum_i64(az);
+            if (lane == i) {
+                mx = tx;
+                my = ty;
+                mz = tz;
             }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
         }
-    }
+        // ---- lanes < n_own: the particle's count and own-bin sums into the window or, outside it,
+        //      the global accumulator
+        if (lane < n_own) {
+            const int b = (int)pmc_profile_bin(ow - 0x80000000u, nbins);
+            int e = b - wmod;
+            e = e < 0 ? e + nbins : e;
+            if (e < wn) (void)__hip_atomic_fetch_add(&wcnt[e], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else atomicAdd(&gcnt[b], 1ull);
+            deposit(b, mx, my, mz);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+    });
     // ---- flush: the window, then the wave sums (int64, exact in any order)
     flush_window();
 #pragma unroll
@@ -5749,11 +5160,34 @@ static size_t lds_bytes(int cap) { return sizeof(float) * (size_t)lds_floats_per
 static int64_t phase_cells(const DevGeom& g, int ncz) { return (int64_t)(g.cps_x / 2) * (g.cps_y / 2) * ncz; }
 
 // 32-bit byte offsets when the disk buffer (halo planes included) is below 4 GiB (every single-GPU
-// 256^3 config), else 64-bit addressing.  The env hooks on top of it are NOT symmetric: only
-// launch_subsweep and launch_pairobs read PMC_FORCE_ADDR64, only the shift reads PMC_SHIFT_OFF32.
+// 256^3 config), else 64-bit addressing.  The env hooks on top of it are NOT symmetric: the sweep and
+// the observables read PMC_FORCE_ADDR64 (addr_off32), only the shift reads PMC_SHIFT_OFF32.
 static bool disk_off32(const DevGeom& g) {
     const int64_t bytes = (int64_t)g.cps_x * g.cps_y * (g.nz_local + 2 * g.halo) * 3 * g.nmax * 4;
     return bytes < ((int64_t)1 << 32);
+}
+// ... unless the test hook PMC_FORCE_ADDR64 takes the 64-bit path for any size.  The hook is latched
+// once per process, at the first launch of any kernel that asks (sweep, rescale or observable)
+static bool addr_off32(const DevGeom& g) {
+    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;
+    return !force64 && disk_off32(g);
+}
+
+// The cell walks' launch shape: the owned cells in runs of kPairObsRun, one wave of 64 per run up to
+// a fixed grid of 4096 waves (4 per SIMD of the chip), which stride over the rest.
+struct WalkGrid {
+    int64_t total;   // owned cells
+    dim3 grid, block;
+};
+static WalkGrid walk_grid(const DevGeom& g) {
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;
+    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
+    return {total, dim3((unsigned)(runs < 4096 ? runs : 4096)), dim3(kWave)};
+}
+// floats of a cell walk's staging (CellWalk): positions of 27 * nmax particles, 32 list entries, and
+// 27 * nmax payload words where one is staged
+static size_t walk_lds_floats(const DevGeom& g, bool payload) {
+    return (size_t)(payload ? 4 : 3) * 27 * (size_t)g.nmax + 32;
 }
 
 // Run-time geometry -> template arguments.  f is a generic lambda; it reads its arguments' ::value.
@@ -5971,9 +5405,7 @@ hipError_t launch_subsweep(const HostGeom& g, float* disk, const int16_t* n, int
                            hipStream_t st, const LaunchTiming* tm, bool solo) {
     const ColourPlanes p = colour_planes(zl_begin, zl_end, oz, g.nz_local);
     if (p.ncz <= 0) return skip_launch(st, tm);
-    // test hook: PMC_FORCE_ADDR64 takes the 64-bit path for any size
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;
-    const bool off32 = !force64 && disk_off32(g);
+    const bool off32 = addr_off32(g);
     if (g.quirks & kQuirksRng) {
         launch_quirk(g, off32, disk, n, ox, oy, oz, sweep, stats, p.cz0, p.ncz, st, tm);
         return hipGetLastError();
@@ -6175,16 +5607,13 @@ hipError_t launch_energy(const DevGeom& g, const float* disk, const int16_t* n,
 hipError_t launch_pairobs(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc,
                           float rmax2, float bscale, int nbins, hipStream_t st) {
     if (nbins < 1 || nbins > kPairObsMaxBins) return hipErrorInvalidValue;
-    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
-    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
-    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
-    const size_t lds = sizeof(float) * (3 * 27 * (size_t)g.nmax + kPairObsRing + 32 + (size_t)nbins);
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_subsweep
-    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+    const WalkGrid wg = walk_grid(g);
+    const size_t lds = sizeof(float) * (walk_lds_floats(g, false) + kPairObsRing + (size_t)nbins);
+    with_nslot(g, addr_off32(g), [&](auto ns, auto off) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool O = decltype(off)::value;
-        hipLaunchKernelGGL((k_pairobs<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, rmax2, bscale,
-                           nbins);
+        hipLaunchKernelGGL((k_pairobs<NS, O>), wg.grid, wg.block, lds, st, g, disk, n, acc, (uint32_t)wg.total, rmax2,
+                           bscale, nbins);
     });
     return hipGetLastError();
 }
@@ -6205,8 +5634,7 @@ hipError_t launch_rdf_long(const DevGeom& g, const float* disk, const int16_t* n
     const dim3 grid((unsigned)(runs < 8192 ? runs : 8192)), block(kWave);
     const size_t lds = sizeof(unsigned) * (size_t)nbins + sizeof(uint16_t) * (size_t)kWave * (size_t)g.nmax;
     const UDivMagic d1 = make_udiv_magic((uint32_t)n1), d2 = make_udiv_magic((uint32_t)(n1 * n1));
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
-    with_bool(!force64 && disk_off32(g), [&](auto off) {
+    with_bool(addr_off32(g), [&](auto off) {
         constexpr bool O = decltype(off)::value;
         hipLaunchKernelGGL((k_rdf_long<O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, shells, d1, d2, rmax2,
                            bscale, nbins);
@@ -6218,15 +5646,12 @@ hipError_t launch_rdf_long(const DevGeom& g, const float* disk, const int16_t* n
 // fixed grid; 5.8 KiB of LDS per wave at nmax 16 (no histogram).
 hipError_t launch_npt_sums(const DevGeom& g, const float* disk, const int16_t* n, unsigned long long* acc,
                            hipStream_t st) {
-    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
-    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
-    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
-    const size_t lds = sizeof(float) * (3 * 27 * (size_t)g.nmax + kPairObsRing + 32);
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
-    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+    const WalkGrid wg = walk_grid(g);
+    const size_t lds = sizeof(float) * (walk_lds_floats(g, false) + kPairObsRing);
+    with_nslot(g, addr_off32(g), [&](auto ns, auto off) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool O = decltype(off)::value;
-        hipLaunchKernelGGL((k_npt_sums<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total);
+        hipLaunchKernelGGL((k_npt_sums<NS, O>), wg.grid, wg.block, lds, st, g, disk, n, acc, (uint32_t)wg.total);
     });
     return hipGetLastError();
 }
@@ -6244,8 +5669,7 @@ hipError_t launch_rescale(const DevGeom& g, float* disk, const int16_t* n, float
     const uint64_t total = (uint64_t)cells * gran;
     const dim3 grid((unsigned)((total + kRescaleThreads - 1) / kRescaleThreads)), block(kRescaleThreads);
     const UDivMagic dg = make_udiv_magic(gran);
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
-    with_bool(!force64 && disk_off32(g), [&](auto off) {
+    with_bool(addr_off32(g), [&](auto off) {
         constexpr bool O = decltype(off)::value;
         if (vec) hipLaunchKernelGGL((k_rescale<4, O>), grid, block, 0, st, g, disk, n, total, dg, gran, s, w_new, clamp_acc);
         else hipLaunchKernelGGL((k_rescale<1, O>), grid, block, 0, st, g, disk, n, total, dg, gran, s, w_new, clamp_acc);
@@ -6263,18 +5687,16 @@ hipError_t launch_clusters(const DevGeom& g, const float* disk, const int16_t* n
     const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells = storage cells
     const int64_t slots = total * g.nmax;
     if (slots >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
-    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
-    const size_t lds_deg = sizeof(float) * (3 * 27 * (size_t)g.nmax + 32 + kClusterDegBins);
-    const size_t lds_link = sizeof(float) * (4 * 27 * (size_t)g.nmax + 32);
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
-    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+    const WalkGrid wg = walk_grid(g);
+    const size_t lds_deg = sizeof(float) * (walk_lds_floats(g, false) + kClusterDegBins);
+    const size_t lds_link = sizeof(float) * walk_lds_floats(g, true);
+    with_nslot(g, addr_off32(g), [&](auto ns, auto off) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool O = decltype(off)::value;
-        hipLaunchKernelGGL((k_cluster_walk<NS, O, false>), grid, block, lds_deg, st, g, disk, n, acc, (uint32_t)total,
-                           rb2, min_neighbours, parent, deg);
-        hipLaunchKernelGGL((k_cluster_walk<NS, O, true>), grid, block, lds_link, st, g, disk, n, acc, (uint32_t)total,
-                           rb2, min_neighbours, parent, deg);
+        hipLaunchKernelGGL((k_cluster_walk<NS, O, false>), wg.grid, wg.block, lds_deg, st, g, disk, n, acc,
+                           (uint32_t)total, rb2, min_neighbours, parent, deg);
+        hipLaunchKernelGGL((k_cluster_walk<NS, O, true>), wg.grid, wg.block, lds_link, st, g, disk, n, acc,
+                           (uint32_t)total, rb2, min_neighbours, parent, deg);
     });
     const int64_t nb = (slots + 255) / 256;
     const dim3 grid_s((unsigned)(nb < 4096 ? nb : 4096)), block_s(256);
@@ -6297,14 +5719,11 @@ hipError_t launch_bond_order(const DevGeom& g, const float* disk, const int16_t*
     const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells = storage cells
     const int64_t slots = total * g.nmax;
     if (slots >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
-    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
-    const size_t stage = 3 * 27 * (size_t)g.nmax + 32;
-    const size_t lds_acc = sizeof(float) * (stage + (size_t)kWave * (2 * l + 1) + (size_t)nq);
-    const size_t lds_conn = sizeof(float) * (stage + 27 * (size_t)g.nmax + (size_t)kWave * kBooOwn + kBooConnBins);
-    const size_t lds_link = sizeof(float) * (4 * 27 * (size_t)g.nmax + 32);
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
-    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+    const dim3 grid = walk_grid(g).grid, block(kWave);
+    const size_t lds_acc = sizeof(float) * (walk_lds_floats(g, false) + (size_t)kWave * (2 * l + 1) + (size_t)nq);
+    const size_t lds_conn = sizeof(float) * (walk_lds_floats(g, true) + (size_t)kWave * kBooOwn + kBooConnBins);
+    const size_t lds_link = sizeof(float) * walk_lds_floats(g, true);
+    with_nslot(g, addr_off32(g), [&](auto ns, auto off) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool O = decltype(off)::value;
         if (l == 4)
@@ -6337,19 +5756,16 @@ hipError_t launch_bond_order_avg(const DevGeom& g, const float* disk, const int1
     const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells = storage cells
     const int64_t slots = total * g.nmax;
     if (slots >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
-    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
+    const dim3 grid = walk_grid(g).grid, block(kWave);
     const int64_t nb = (slots + 255) / 256;
     const dim3 grid_s((unsigned)(nb < 4096 ? nb : 4096)), block_s(256);
-    const size_t stage = 3 * 27 * (size_t)g.nmax + 32;
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
-    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+    with_nslot(g, addr_off32(g), [&](auto ns, auto off) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool O = decltype(off)::value;
         auto pass = [&](auto lc) {
             constexpr int L = decltype(lc)::value;
-            const size_t lds_acc = sizeof(float) * (stage + (size_t)kWave * (2 * L + 1) + 1);
-            const size_t lds_avg = sizeof(float) * (stage + 27 * (size_t)g.nmax + (size_t)kWave * (2 * L + 1) + (size_t)nq);
+            const size_t lds_acc = sizeof(float) * (walk_lds_floats(g, false) + (size_t)kWave * (2 * L + 1) + 1);
+            const size_t lds_avg = sizeof(float) * (walk_lds_floats(g, true) + (size_t)kWave * (2 * L + 1) + (size_t)nq);
             hipLaunchKernelGGL((k_boo_accum<NS, O, L>), grid, block, lds_acc, st, g, disk, n, boo_scratch, (uint32_t)total,
                                rb2, 1, rec);
             hipLaunchKernelGGL(k_boo_unit, grid_s, block_s, 0, st, n, rec, (uint32_t)slots, (uint32_t)g.nmax);
@@ -6371,17 +5787,14 @@ hipError_t launch_probe(const DevGeom& g, const float* disk, const int16_t* n, u
     if (nbins < 1 || nbins > kProbeMaxBins || bw4 < 1) return hipErrorInvalidValue;
     if (mode != PMC_PROBE_INSERT && mode != PMC_PROBE_REAL) return hipErrorInvalidValue;
     if (mode == PMC_PROBE_INSERT && (k_per_cell < 1 || k_per_cell > PMC_PROBE_MAX_K)) return hipErrorInvalidValue;
-    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
-    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
-    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
-    const size_t lds = sizeof(float) * (3 * 27 * (size_t)g.nmax + 32 + 3 * (size_t)nbins);
+    const WalkGrid wg = walk_grid(g);
+    const size_t lds = sizeof(float) * (walk_lds_floats(g, false) + 3 * (size_t)nbins);
     const float inv_bw = 1.0f / (float)bw4;
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
-    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+    with_nslot(g, addr_off32(g), [&](auto ns, auto off) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool O = decltype(off)::value;
-        hipLaunchKernelGGL((k_probe<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, mode, k_per_cell,
-                           sample, (long long)lo4, (long long)bw4, inv_bw, nbins);
+        hipLaunchKernelGGL((k_probe<NS, O>), wg.grid, wg.block, lds, st, g, disk, n, acc, (uint32_t)wg.total, mode,
+                           k_per_cell, sample, (long long)lo4, (long long)bw4, inv_bw, nbins);
     });
     return hipGetLastError();
 }
@@ -6395,11 +5808,10 @@ hipError_t launch_exchange(const DevGeom& g, float* disk, int16_t* n, unsigned l
     if (k_per_cell < 1 || k_per_cell > PMC_GC_MAX_K || g.halo > 1 || ((ox | oy | oz) & ~1)) return hipErrorInvalidValue;
     const int64_t active = (int64_t)(g.cps_x / 2) * (g.cps_y / 2) * (g.nz_local / 2);
     const dim3 grid((unsigned)(active < 8192 ? active : 8192)), block(kWave);
-    const size_t lds = sizeof(float) * (3 * 27 * (size_t)g.nmax + 32);
+    const size_t lds = sizeof(float) * walk_lds_floats(g, false);
     GcTable tab;
     for (int i = 0; i < 64; ++i) tab.a[i] = i < g.nmax ? table[i] : 0.0f;
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_probe
-    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+    with_nslot(g, addr_off32(g), [&](auto ns, auto off) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool O = decltype(off)::value;
         hipLaunchKernelGGL((k_exchange<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)active, ox, oy, oz,
@@ -6423,8 +5835,7 @@ hipError_t launch_sk(const DevGeom& g, const float* disk, const int16_t* n, unsi
     if (nk <= 32)
         for (lgp = 0; (1 << lgp) < nk; ++lgp) {}
     const float scx = pmc_sk_scale(g.Lx), scy = pmc_sk_scale(g.Ly), scz = pmc_sk_scale(g.Lz);
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_probe
-    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+    with_nslot(g, addr_off32(g), [&](auto ns, auto off) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool O = decltype(off)::value;
         hipLaunchKernelGGL((k_sk<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, hkl, nk, lgp, scx,
@@ -6442,17 +5853,14 @@ hipError_t launch_profile(const DevGeom& g, const float* disk, const int16_t* n,
     if (axis < 0 || axis > 2) return hipErrorInvalidValue;
     const int cps_a = axis == 0 ? g.cps_x : (axis == 1 ? g.cps_y : g.cps_z);
     if (nbins < 1 || nbins > pmc_profile_max_bins(cps_a) || nbins > kProfMaxBins) return hipErrorInvalidValue;
-    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
-    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
-    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
-    const size_t lds = sizeof(float) * (3 * 27 * (size_t)g.nmax + 32) + (size_t)kProfWin * (3 * 8 + 4);
+    const WalkGrid wg = walk_grid(g);
+    const size_t lds = sizeof(float) * walk_lds_floats(g, false) + (size_t)kProfWin * (3 * 8 + 4);
     const float scale = pmc_sk_scale(axis == 0 ? g.Lx : (axis == 1 ? g.Ly : g.Lz));
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
-    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+    with_nslot(g, addr_off32(g), [&](auto ns, auto off) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool O = decltype(off)::value;
-        hipLaunchKernelGGL((k_profile<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, axis, nbins,
-                           cps_a, scale);
+        hipLaunchKernelGGL((k_profile<NS, O>), wg.grid, wg.block, lds, st, g, disk, n, acc, (uint32_t)wg.total, axis,
+                           nbins, cps_a, scale);
     });
     return hipGetLastError();
 }
@@ -6465,17 +5873,14 @@ hipError_t launch_profile_ik(const DevGeom& g, const float* disk, const int16_t*
     if (axis < 0 || axis > 2) return hipErrorInvalidValue;
     const int cps_a = axis == 0 ? g.cps_x : (axis == 1 ? g.cps_y : g.cps_z);
     if (nbins < 1 || nbins > pmc_profile_max_bins(cps_a) || nbins > kProfMaxBins) return hipErrorInvalidValue;
-    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells
-    const int64_t runs = (total + kPairObsRun - 1) / kPairObsRun;
-    const dim3 grid((unsigned)(runs < 4096 ? runs : 4096)), block(kWave);
-    const size_t lds = sizeof(float) * (4 * 27 * (size_t)g.nmax + 32) + (size_t)kProfIkWin * (3 * 8 + 4);
+    const WalkGrid wg = walk_grid(g);
+    const size_t lds = sizeof(float) * walk_lds_floats(g, true) + (size_t)kProfIkWin * (3 * 8 + 4);
     const float scale = pmc_sk_scale(axis == 0 ? g.Lx : (axis == 1 ? g.Ly : g.Lz));
-    static const bool force64 = std::getenv("PMC_FORCE_ADDR64") != nullptr;   // test hook, as launch_pairobs
-    with_nslot(g, !force64 && disk_off32(g), [&](auto ns, auto off) {
+    with_nslot(g, addr_off32(g), [&](auto ns, auto off) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool O = decltype(off)::value;
-        hipLaunchKernelGGL((k_profile_ik<NS, O>), grid, block, lds, st, g, disk, n, acc, (uint32_t)total, axis, nbins,
-                           cps_a, scale);
+        hipLaunchKernelGGL((k_profile_ik<NS, O>), wg.grid, wg.block, lds, st, g, disk, n, acc, (uint32_t)wg.total, axis,
+                           nbins, cps_a, scale);
     });
     return hipGetLastError();
 }
