@@ -522,6 +522,40 @@ typedef struct pmc_boo_avg_obs {
 } pmc_boo_avg_obs;
 int pmc_bond_order_avg(pmc_ctx* ctx, float r_bond, int nq, int n2, uint64_t* h_qa4, uint64_t* h_qa6, uint64_t* h_joint,
                        int32_t* h_slot, pmc_boo_avg_obs* out);
+/* Common-neighbour analysis of the owned cells' particles, defined bit for bit in pmc_cna.h: the
+ * Honeycutt-Andersen signature (ncn, nb, lc) of every ordered bond (partners with r <= r_bond,
+ * pmc_cluster.h's walk; adjacency among a particle's neighbours on the positions its own walk sees),
+ * the type of every particle by the fixed-cutoff rules (OTHER 0, FCC 1, HCP 2, BCC 3, ICO 4) and the
+ * clusters of the particles whose type is in type_mask (bit t selects type t) under "bonded in either
+ * direction", labelled as pmc_clusters labels them.  The reference has no such observable.  All
+ * pointers are HOST pointers.  h_sig[2048]: entry min(ncn, 7) * 256 + min(nb, 15) * 16 + min(lc, 15)
+ * counts the ordered bonds with that signature.  h_size[nbins]: as in pmc_clusters.  h_record (may be
+ * NULL): storage_cells * nmax records of 8 int32 in slot order: type, deg, n421, n422, n444, n666, n555,
+ * 0; an empty slot holds type -1 and zeros.  h_label (may be NULL): as in pmc_clusters, -1 for a
+ * particle whose type is not in the mask.  A particle with more than 64 bonds is over capacity: type
+ * OTHER, counted in out->over, no signatures.  type_mask = 0 skips the clusters (counts 0,
+ * largest_label -1, labels -1).
+ * PMC_ERR_ARG (outputs untouched) for a null h_sig, h_size or out, r_bond not finite, <= 0 or > w,
+ * type_mask with bits above 4, nbins outside 1..4096, storage_cells * nmax >= 2^31, and for any slab
+ * context (halo != 0): a particle's neighbours' neighbours and a cluster can cross a slab face.  Runs on
+ * the context stream and synchronises; state, statistics, exchange counters, error flags and the
+ * energy are left unchanged.  Device scratch (32 bytes per slot, plus pmc_clusters' 10 bytes per slot,
+ * which the calls share) is allocated on the first call and freed by pmc_destroy; a failed allocation
+ * returns PMC_ERR_HIP and leaves the context usable. */
+typedef struct pmc_cna_obs {
+    int64_t particles;      /* particles in owned cells */
+    int64_t bonds;          /* ordered pairs with r2 <= rb2 (the sum of the degrees) */
+    int64_t over;           /* particles with deg > 64 (type OTHER, no signatures) */
+    int64_t types[5];       /* particles per type, OTHER first (the over-capacity ones included) */
+    int64_t marked;         /* particles whose type is in type_mask */
+    int64_t marked_bonds;   /* ordered pairs with r2 <= rb2 and both ends marked */
+    int64_t clusters;       /* clusters (components of the marked particles) */
+    int64_t largest;        /* size of the largest cluster (0 without clusters) */
+    int64_t largest_label;  /* the smallest label among the clusters of that size (-1 without clusters) */
+    int64_t sum_s2;         /* sum over clusters of size^2 */
+} pmc_cna_obs;
+int pmc_common_neighbours(pmc_ctx* ctx, float r_bond, uint32_t type_mask, int nbins, uint64_t* h_sig,
+                          uint64_t* h_size, int32_t* h_record, int32_t* h_label, pmc_cna_obs* out);
 /* The pair histogram beyond the cutoff, defined bit for bit in pmc_rdf.h: the ORDERED pairs (i in an
  * owned cell, j in the cube of (2R+1)^3 cells round it, periodic wrap) closer than r_max, for r_max up
  * to several cell widths; R = pmc_rdf_shells(r_max, w) is the smallest number of shells that holds

@@ -15,6 +15,7 @@
 #include "../../include/pmc_pairobs.h"
 #include "../../include/pmc_rdf.h"
 #include "../../include/pmc_cluster.h"
+#include "../../include/pmc_cna.h"
 #include "../../include/pmc_boo.h"
 #include "../../include/pmc_boo_avg.h"
 #include "../../include/pmc_probe.h"
@@ -329,7 +330,8 @@ void pmc_destroy(pmc_ctx* c) {
     if (c->gc_acc) (void)hipFree(c->gc_acc);
     if (c->npt_acc) (void)hipFree(c->npt_acc);
     for (void* m : {(void*)c->cl_parent, (void*)c->cl_size, (void*)c->cl_deg, (void*)c->cl_acc, (void*)c->boo_rec,
-                    (void*)c->boo_acc, (void*)c->boo_avg_slot, (void*)c->boo_avg_acc})
+                    (void*)c->boo_acc, (void*)c->boo_avg_slot, (void*)c->boo_avg_acc, (void*)c->cna_rec,
+                    (void*)c->cna_acc})
         if (m) (void)hipFree(m);
     if (c->flags) (void)hipFree(c->flags);
     if (c->ovf) (void)hipFree(c->ovf);
@@ -907,6 +909,84 @@ int pmc_bond_order(pmc_ctx* c, int l, float r_bond, int c8, int min_conn, int nq
     for (int b = 0; b < PMC_BOO_CONN_BINS; ++b) h_conn[b] = (uint64_t)s[(size_t)kBooHead + (size_t)b];
     for (int b = 0; b < nq; ++b) h_q[b] = (uint64_t)s[(size_t)kBooHead + kBooConnBins + (size_t)b];
     for (int b = 0; b < nbins; ++b) h_size[b] = (uint64_t)tail[(size_t)kClusterTail + (size_t)b];
+    return PMC_OK;
+}
+
+int pmc_common_neighbours(pmc_ctx* c, float r_bond, uint32_t type_mask, int nbins, uint64_t* h_sig, uint64_t* h_size,
+                          int32_t* h_record, int32_t* h_label, pmc_cna_obs* out) {
+    if (!c || !h_sig || !h_size || !out) return fail(PMC_ERR_ARG, "bad argument");
+    if (c->P.halo != 0)
+        return fail(PMC_ERR_ARG, "pmc_common_neighbours: whole-box contexts only (halo == 0): a particle's neighbours' "
+                                 "neighbours and a cluster can cross a slab face");
+    if (!std::isfinite(r_bond) || !(r_bond > 0.0f) || r_bond > c->P.w)
+        return fail(PMC_ERR_ARG, "pmc_common_neighbours: r_bond must be finite, > 0 and <= w");
+    if (type_mask >> PMC_CNA_TYPES) return fail(PMC_ERR_ARG, "pmc_common_neighbours: type_mask has bits 0..4 only");
+    if (nbins < 1 || nbins > PMC_CNA_MAX_BINS) return fail(PMC_ERR_ARG, "pmc_common_neighbours: nbins must be in 1..4096");
+    const int64_t slots64 = c->cells * (int64_t)c->P.nmax;
+    if (slots64 >= ((int64_t)1 << 31))
+        return fail(PMC_ERR_ARG, "pmc_common_neighbours: storage_cells * nmax must be below 2^31");
+    const size_t slots = (size_t)slots64;
+    if (int rj = slab_join(c)) return rj;
+    if (int ra = cluster_scratch(c, slots, "pmc_common_neighbours: scratch allocation")) return ra;
+    if (!c->cna_acc) {
+        // both or none
+        hipError_t ea = hipMalloc(&c->cna_rec, sizeof(int32_t) * kCnaRecord * slots);
+        if (ea == hipSuccess) ea = hipMalloc(&c->cna_acc, sizeof(unsigned long long) * cna_acc_words());
+        if (ea != hipSuccess) {
+            if (c->cna_rec) (void)hipFree(c->cna_rec);
+            c->cna_rec = nullptr;
+            c->cna_acc = nullptr;
+            (void)hipGetLastError();   // the context stays usable
+            return hip_fail(ea, "pmc_common_neighbours: scratch allocation");
+        }
+    }
+    const size_t cwords = cluster_acc_words(nbins);
+    if (type_mask) {
+        PMC_HIP(hipMemsetAsync(c->cl_parent, 0xFF, sizeof(int) * slots, c->stream));
+        PMC_HIP(hipMemsetAsync(c->cl_size, 0, sizeof(unsigned) * slots, c->stream));
+        PMC_HIP(hipMemsetAsync(c->cl_acc, 0, sizeof(unsigned long long) * cwords, c->stream));
+    }
+    PMC_HIP(hipMemsetAsync(c->cna_acc, 0, sizeof(unsigned long long) * cna_acc_words(), c->stream));
+    hipError_t e = launch_cna(c->G, c->disk[c->cur], c->n[c->cur], pmc_cutoff_r2(r_bond), type_mask, nbins, c->cna_rec,
+                              c->cl_parent, c->cl_size, c->cl_deg, c->cna_acc, c->cl_acc, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "common-neighbour analysis launch");
+    std::vector<unsigned long long> hc(type_mask ? cwords : 0), ha(cna_acc_words());
+    PMC_HIP(hipMemcpyAsync(ha.data(), c->cna_acc, sizeof(unsigned long long) * ha.size(), hipMemcpyDeviceToHost, c->stream));
+    if (type_mask) {
+        PMC_HIP(hipMemcpyAsync(hc.data(), c->cl_acc, sizeof(unsigned long long) * cwords, hipMemcpyDeviceToHost, c->stream));
+        if (h_label)
+            PMC_HIP(hipMemcpyAsync(h_label, c->cl_parent, sizeof(int32_t) * slots, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (h_record)
+        PMC_HIP(hipMemcpyAsync(h_record, c->cna_rec, sizeof(int32_t) * kCnaRecord * slots, hipMemcpyDeviceToHost, c->stream));
+    PMC_HIP(hipStreamSynchronize(c->stream));
+    constexpr size_t per = (size_t)kCnaHead + kCnaSig;
+    std::vector<unsigned long long> s(per, 0ull);
+    for (int k = 0; k < kCnaCopies; ++k)
+        for (size_t i = 0; i < per; ++i) s[i] += ha[(size_t)k * per + i];
+    out->bonds = (int64_t)s[0];
+    out->particles = (int64_t)s[1];
+    out->over = (int64_t)s[2];
+    for (int t = 0; t < PMC_CNA_TYPES; ++t) out->types[t] = (int64_t)s[3 + (size_t)t];
+    out->marked = (int64_t)s[3 + PMC_CNA_TYPES];
+    for (int b = 0; b < PMC_CNA_SIG; ++b) h_sig[b] = (uint64_t)s[(size_t)kCnaHead + (size_t)b];
+    if (type_mask) {
+        unsigned long long marked_bonds = 0;
+        for (int k = 0; k < kClusterCopies; ++k) marked_bonds += hc[(size_t)k * (kClusterHead + kClusterDegBins) + 3];
+        const unsigned long long* tail = hc.data() + (size_t)kClusterCopies * (kClusterHead + kClusterDegBins);
+        out->marked_bonds = (int64_t)marked_bonds;
+        out->clusters = (int64_t)tail[0];
+        out->sum_s2 = (int64_t)tail[1];
+        out->largest = (int64_t)(tail[2] >> 32);
+        out->largest_label = tail[0] ? (int64_t)(0x7FFFFFFFu - (uint32_t)(tail[2] & 0xFFFFFFFFull)) : -1;
+        for (int b = 0; b < nbins; ++b) h_size[b] = (uint64_t)tail[(size_t)kClusterTail + (size_t)b];
+    } else {
+        out->marked_bonds = out->clusters = out->sum_s2 = out->largest = 0;
+        out->largest_label = -1;
+        for (int b = 0; b < nbins; ++b) h_size[b] = 0;
+        if (h_label)
+            for (size_t i = 0; i < slots; ++i) h_label[i] = -1;
+    }
     return PMC_OK;
 }
 

@@ -44,6 +44,9 @@ struct pmc_ctx {
     // neighbour-averaged bond order: shares boo_rec / boo_acc above; its own scratch, allocated together on first use
     int* boo_avg_slot = nullptr;               // storage_cells * nmax entries of kBooAvgSlot int32
     unsigned long long* boo_avg_acc = nullptr; // boo_avg_words(kBooAvgMaxBins, kBooAvgMaxJoint)
+    // common-neighbour analysis: shares cl_* above; its own scratch is allocated together on first use
+    int* cna_rec = nullptr;                    // storage_cells * nmax records of kCnaRecord int32
+    unsigned long long* cna_acc = nullptr;     // cna_acc_words()
     unsigned long long* gc_acc = nullptr;      // exchange moves: accumulator copies (allocated on first use; kept until reset)
     // volume moves: the pair-sum accumulator copies and the clamp counter (allocated on first use), and
     // the host-side counters pmc_npt_stats_read returns

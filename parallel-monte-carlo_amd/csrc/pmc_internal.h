@@ -273,6 +273,25 @@ constexpr size_t boo_acc_words(int nq) { return (size_t)kBooCopies * boo_acc_str
 hipError_t launch_bond_order(const DevGeom& g, const float* disk, const int16_t* n, int l, float rb2, int c8,
                              int min_conn, int nq, int nbins, int* rec, int* parent, unsigned* size, uint16_t* nconn,
                              unsigned long long* boo_acc, unsigned long long* cl_acc, hipStream_t st);
+// common-neighbour analysis (k_cna, then k_cluster_walk's link form, k_cluster_flatten and k_cluster_count;
+// pmc_cna.h) of a whole-box context with slots = cells * nmax < 2^31.  rec: one record of kCnaRecord int32
+// per slot (type, deg, n421, n422, n444, n666, n555, 0; type -1 in an empty slot), every slot written by
+// the call.  parent, size, flag and cl_acc are launch_clusters' parent, size, deg and acc, prepared in the
+// same way and touched only when type_mask != 0: flag takes 1 for a marked particle and 0 for another,
+// cl_acc's copies [3] the ordered bonds between marked particles and its tail the cluster counts; after
+// the call parent holds the labels.  cna_acc, zeroed on st before the call: kCnaCopies copies of kCnaHead +
+// kCnaSig counters the host sums: [0] ordered bonds, [1] owned particles, [2] particles over capacity,
+// [3..7] particles per type, [8] marked particles, then from kCnaHead the signature table.
+constexpr int kCnaCopies = 32;
+constexpr int kCnaHead = 16;
+constexpr int kCnaSig = 2048;          // PMC_CNA_SIG
+constexpr int kCnaMaxNb = 64;          // PMC_CNA_MAX_NB
+constexpr int kCnaRecord = 8;          // PMC_CNA_RECORD
+static_assert((kCnaCopies & (kCnaCopies - 1)) == 0, "accumulator copies: a power of two");
+constexpr size_t cna_acc_words() { return (size_t)kCnaCopies * (kCnaHead + kCnaSig); }
+hipError_t launch_cna(const DevGeom& g, const float* disk, const int16_t* n, float rb2, uint32_t type_mask, int nbins,
+                      int* rec, int* parent, unsigned* size, uint16_t* flag, unsigned long long* cna_acc,
+                      unsigned long long* cl_acc, hipStream_t st);
 // neighbour-averaged bond order (pmc_boo_avg.h) of a whole-box context with slots = cells * nmax < 2^31:
 // per l in 4, 6: k_boo_accum<.., l> (its accumulators go to boo_scratch, boo_acc_words(1) counters that
 // nobody reads), k_boo_unit (Q_m -> u_m in rec, in place) and k_boo_avg<.., l>; then k_boo_joint.  rec:

@@ -28,6 +28,7 @@
 #include "../../include/pmc_pairobs.h"
 #include "../../include/pmc_rdf.h"
 #include "../../include/pmc_cluster.h"
+#include "../../include/pmc_cna.h"
 #include "../../include/pmc_boo.h"
 #include "../../include/pmc_boo_avg.h"
 #include "../../include/pmc_probe.h"
@@ -3223,6 +3224,188 @@ __global__ __launch_bounds__(256) void k_cluster_count(const int* __restrict__ p
 }
 
 // ------------------------------------------------------------------------------------------
+// common-neighbour analysis (include/pmc_cna.h): k_cna, a cell walk (CellWalk without a payload; its
+// pmc_box_d2 filter is conservative for r_bond <= w, and every neighbour of an own particle is
+// staged), then the cluster analysis' link walk, flatten and count on the marked particles, with
+// flag[] (1 marked, 0 not) as the degrees and 1 as min_neighbours.
+//
+// Per own particle i (wave-uniform loop; own particles are staged first, lane i of block 0):
+//   list   every lane tests its staged partner against i (blocks of 64); the hits are ballot-
+//          compacted into nbx/nby/nbz (64 shifted positions of i's frame).  deg counts every hit;
+//          deg > 64 marks the particle over capacity and ends its analysis.
+//   rows   lane a < deg keeps neighbour a in registers; neighbour b = 0..deg-1 is broadcast by
+//          readlane and lane a sets bit b of its own row when adj_i(a, b).  adj_i is symmetric bit
+//          for bit (pmc_cna.h), so lane a's row is row a of the matrix; the 64 rows go to LDS.
+//   sig    lane j < deg owns bond (i, j): C = row[j], ncn = popcount(C); a flood fill over bit masks
+//          visits every component of (C, bonds) once, reading row[a] & C for each of its members:
+//          the popcounts add up to twice the component's bonds (lc = the largest, nb = their sum).
+//   table  one ds_add_u32 per bond into the wave's private table of 2048 signatures in LDS, flushed
+//          once at the end: a wave visits at most cells / 4096 + 2 * kPairObsRun cells of at most
+//          64 * 64 counted bonds each and cells * 3 * nmax < 2^32 (pmc_create), so a bin stays below
+//          2^32 / 192 + 2^16.
+//   type   the five named signatures are counted by ballot; lane i keeps particle i's record.
+// After the loop lane s < nmax writes the record of slot s (32 bytes; type -1 in an empty slot),
+// the own lanes their flag and initial parent.  Integers only, independent of every order: equal to
+// tests/cna_ref.c bit for bit.
+// ------------------------------------------------------------------------------------------
+template <int NSLOT, bool OFF32>
+__global__ __launch_bounds__(kWave) void k_cna(DevGeom g, const float* __restrict__ disk,
+                                               const int16_t* __restrict__ ncnt,
+                                               unsigned long long* __restrict__ acc, uint32_t total_cells, float rb2,
+                                               uint32_t type_mask, int* __restrict__ rec, int* __restrict__ parent,
+                                               uint16_t* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long qsm[];
+    const int lane = threadIdx.x;
+    const int nm = g.nmax;
+    const int cap = 27 * nm;
+    unsigned long long* rows = qsm;                    // row a of the adjacency among N(i): kWave words
+    unsigned* table = (unsigned*)(rows + kWave);       // kCnaSig signature counters of this wave
+    float* nbx = (float*)(table + kCnaSig);            // N(i): kCnaMaxNb shifted positions
+    float* nby = nbx + kCnaMaxNb;
+    float* nbz = nby + kCnaMaxNb;
+    float* ex_ = nbz + kCnaMaxNb;
+    float* ey_ = ex_ + cap;
+    float* ez_ = ex_ + 2 * cap;
+    int* inv_l = (int*)(ex_ + 3 * cap);                // list entry -> stencil lane (32 ints)
+    unsigned long long n_bonds = 0, n_part = 0, n_over = 0, n_marked = 0;   // wave-uniform
+    unsigned long long n_type[PMC_CNA_TYPES] = {0, 0, 0, 0, 0};
+    for (int b = lane; b < kCnaSig; b += kWave) table[b] = 0u;
+    CellWalk<NSLOT, OFF32> walk(g, disk, ncnt, ex_, nullptr, inv_l);
+    walk.run(total_cells, [&](const WalkCell& cell, int S, int n_own) {
+        const int id0 = cell.kc * nm;   // id of the own cell's slot 0
+        n_part += (unsigned long long)n_own;
+        int r_type = -1, r_deg = 0, r_n0 = 0, r_n1 = 0, r_n2 = 0, r_n3 = 0, r_n4 = 0;   // lane s: record of slot s
+        if (n_own > 0) {
+            const int l0 = lane < S ? lane : 0;
+            const float ox = ex_[l0], oy = ey_[l0], oz = ez_[l0];   // block 0 (own at lanes < n_own)
+            for (int i = 0; i < n_own; ++i) {
+                const float xi = as_f(__builtin_amdgcn_readlane(as_i(ox), i));
+                const float yi = as_f(__builtin_amdgcn_readlane(as_i(oy), i));
+                const float zi = as_f(__builtin_amdgcn_readlane(as_i(oz), i));
+                // ---- list: N(i) in staged order, compacted
+                int deg = 0;
+                for (int jb = 0; jb < S; jb += kWave) {
+                    const int j = jb + lane;
+                    const bool vj = j < S;
+                    float xj = ox, yj = oy, zj = oz;
+                    if (jb > 0) {
+                        const int jj = vj ? j : 0;
+                        xj = ex_[jj];
+                        yj = ey_[jj];
+                        zj = ez_[jj];
+                    }
+                    const float r2 = pmc_r2(xi - xj, yi - yj, zi - zj);
+                    const bool hit = vj && r2 <= rb2 && j != i;
+                    const unsigned long long im = __builtin_amdgcn_ballot_w64(hit);
+                    const int dst = deg + mbcnt64(im);
+                    if (hit && dst < kCnaMaxNb) {
+                        nbx[dst] = xj;
+                        nby[dst] = yj;
+                        nbz[dst] = zj;
+                    }
+                    deg += __popcll(im);
+                }
+                n_bonds += (unsigned long long)deg;
+                int mt = PMC_CNA_OTHER, c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;
+                if (deg > kCnaMaxNb) {
+                    ++n_over;
+                } else if (deg > 0) {
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    // ---- rows: lane a holds neighbour a, b is broadcast
+                    const bool va = lane < deg;
+                    const int la = va ? lane : 0;
+                    const float ax = nbx[la], ay = nby[la], az = nbz[la];
+                    unsigned long long myrow = 0ull;
+                    for (int b = 0; b < deg; ++b) {
+                        const float bx = as_f(__builtin_amdgcn_readlane(as_i(ax), b));
+                        const float by = as_f(__builtin_amdgcn_readlane(as_i(ay), b));
+                        const float bz = as_f(__builtin_amdgcn_readlane(as_i(az), b));
+                        const float r2 = pmc_r2(ax - bx, ay - by, az - bz);
+                        myrow |= (r2 <= rb2 && lane != b) ? (1ull << b) : 0ull;
+                    }
+                    rows[lane] = va ? myrow : 0ull;
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    // ---- sig: lane j owns bond (i, j)
+                    int named = -1;
+                    if (va) {
+                        const unsigned long long C = myrow;
+                        unsigned long long rem = C;
+                        int nb2 = 0, lc = 0;
+                        while (rem) {
+                            unsigned long long comp = rem & (0ull - rem), fr = comp;
+                            int e2 = 0;   // twice the bonds of this component
+                            while (fr) {
+                                unsigned long long nx = 0ull;
+                                while (fr) {
+                                    const int a = (int)__builtin_ctzll(fr);
+                                    fr &= fr - 1ull;
+                                    const unsigned long long r = rows[a] & C;
+                                    e2 += __popcll(r);
+                                    nx |= r;
+                                }
+                                fr = nx & ~comp;
+                                comp |= fr;
+                            }
+                            rem &= ~comp;
+                            nb2 += e2;
+                            lc = (e2 >> 1) > lc ? (e2 >> 1) : lc;
+                        }
+                        const int ncn = __popcll(C), nb = nb2 >> 1;
+                        named = pmc_cna_named(ncn, nb, lc);
+                        (void)__hip_atomic_fetch_add(&table[pmc_cna_sig_index(ncn, nb, lc)], 1u, __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    c0 = __popcll(__builtin_amdgcn_ballot_w64(named == 0));
+                    c1 = __popcll(__builtin_amdgcn_ballot_w64(named == 1));
+                    c2 = __popcll(__builtin_amdgcn_ballot_w64(named == 2));
+                    c3 = __popcll(__builtin_amdgcn_ballot_w64(named == 3));
+                    c4 = __popcll(__builtin_amdgcn_ballot_w64(named == 4));
+                    mt = pmc_cna_type(deg, c0, c1, c2, c3, c4);
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next particle rewrites list and rows
+                }
+                if (lane == i) {
+                    r_type = mt;
+                    r_deg = deg;
+                    r_n0 = c0;
+                    r_n1 = c1;
+                    r_n2 = c2;
+                    r_n3 = c3;
+                    r_n4 = c4;
+                }
+            }
+        }
+        // ---- records of all nmax slots, flags and initial parents of the own particles
+        if (lane < nm) {
+            int4* dst = reinterpret_cast<int4*>(rec + (size_t)(id0 + lane) * kCnaRecord);
+            dst[0] = make_int4(r_type, r_deg, r_n0, r_n1);
+            dst[1] = make_int4(r_n2, r_n3, r_n4, 0);
+        }
+        const bool own = lane < n_own;
+        const bool marked = own && ((type_mask >> (r_type & 7)) & 1u);
+        if (type_mask != 0u && own) {
+            flag[id0 + lane] = marked ? (uint16_t)1 : (uint16_t)0;
+            if (marked) parent[id0 + lane] = id0 + lane;
+        }
+        n_marked += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(marked));
+#pragma unroll
+        for (int t = 0; t < PMC_CNA_TYPES; ++t)
+            n_type[t] += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(own && r_type == t));
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next cell's staging overwrites ex_
+    });
+    // ---- flush: [bonds, particles, over, types[5], marked], then this wave's nonzero signatures
+    unsigned long long* mine = acc + (size_t)(blockIdx.x & (kCnaCopies - 1)) * (size_t)(kCnaHead + kCnaSig);
+    unsigned long long head = lane == 0 ? n_bonds : (lane == 1 ? n_part : (lane == 2 ? n_over : n_marked));
+#pragma unroll
+    for (int t = 0; t < PMC_CNA_TYPES; ++t) head = lane == 3 + t ? n_type[t] : head;
+    if (lane < 4 + PMC_CNA_TYPES && head != 0) atomicAdd(&mine[lane], head);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    for (int b = lane; b < kCnaSig; b += kWave) {
+        const unsigned h = table[b];
+        if (h) atomicAdd(&mine[kCnaHead + b], (unsigned long long)h);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // bond-orientational order (include/pmc_boo.h): two further walks that keep a private copy of the
 // cell walk (CellWalk's stencil, staging order, chunks, filter and capacity; on the shared form they
 // ran 1-2 % slower), then the cluster analysis' own link, flatten and count launches on
@@ -5742,6 +5925,41 @@ hipError_t launch_bond_order(const DevGeom& g, const float* disk, const int16_t*
     hipLaunchKernelGGL(k_cluster_flatten, grid_s, block_s, 0, st, parent, size, (uint32_t)slots);
     hipLaunchKernelGGL(k_cluster_count, grid_s, block_s, sizeof(unsigned) * (size_t)nbins, st, parent, size,
                        (uint32_t)slots, cl_acc + (size_t)kClusterCopies * (kClusterHead + kClusterDegBins), nbins);
+    return hipGetLastError();
+}
+
+// The common-neighbour analysis' launches (pmc_internal.h states the buffers): k_cna on launch_clusters'
+// grid, then, unless type_mask is 0, the cluster analysis' link walk, flatten and count, unchanged, with
+// the marked flags as the degrees and 1 as min_neighbours.  LDS per wave of k_cna: 9.25 KiB (rows,
+// signature table, neighbour list) and the staging: 14.4 KiB at nmax 16.
+hipError_t launch_cna(const DevGeom& g, const float* disk, const int16_t* n, float rb2, uint32_t type_mask, int nbins,
+                      int* rec, int* parent, unsigned* size, uint16_t* flag, unsigned long long* cna_acc,
+                      unsigned long long* cl_acc, hipStream_t st) {
+    if (nbins < 1 || nbins > kClusterMaxBins || g.halo != 0 || (type_mask >> PMC_CNA_TYPES) != 0u || g.nmax > kWave)
+        return hipErrorInvalidValue;
+    const int64_t total = (int64_t)g.cps_x * g.cps_y * g.nz_local;   // owned cells = storage cells
+    const int64_t slots = total * g.nmax;
+    if (slots >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const dim3 grid = walk_grid(g).grid, block(kWave);
+    const size_t lds_cna = sizeof(unsigned long long) * kWave + sizeof(unsigned) * kCnaSig +
+                           sizeof(float) * (3 * (size_t)kCnaMaxNb + walk_lds_floats(g, false));
+    const size_t lds_link = sizeof(float) * walk_lds_floats(g, true);
+    with_nslot(g, addr_off32(g), [&](auto ns, auto off) {
+        constexpr int NS = decltype(ns)::value;
+        constexpr bool O = decltype(off)::value;
+        hipLaunchKernelGGL((k_cna<NS, O>), grid, block, lds_cna, st, g, disk, n, cna_acc, (uint32_t)total, rb2, type_mask,
+                           rec, parent, flag);
+        if (type_mask != 0u)
+            hipLaunchKernelGGL((k_cluster_walk<NS, O, true>), grid, block, lds_link, st, g, disk, n, cl_acc,
+                               (uint32_t)total, rb2, 1, parent, flag);
+    });
+    if (type_mask != 0u) {
+        const int64_t nb = (slots + 255) / 256;
+        const dim3 grid_s((unsigned)(nb < 4096 ? nb : 4096)), block_s(256);
+        hipLaunchKernelGGL(k_cluster_flatten, grid_s, block_s, 0, st, parent, size, (uint32_t)slots);
+        hipLaunchKernelGGL(k_cluster_count, grid_s, block_s, sizeof(unsigned) * (size_t)nbins, st, parent, size,
+                           (uint32_t)slots, cl_acc + (size_t)kClusterCopies * (kClusterHead + kClusterDegBins), nbins);
+    }
     return hipGetLastError();
 }
 

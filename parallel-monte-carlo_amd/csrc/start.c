@@ -6,7 +6,7 @@
  *         [--sigma 0.5] [--w 2.5] [--seed 1234] [--every 1] [--graph]
  *         [--dump FILE] [--save FILE] [--restart FILE] [--pairobs NBINS] [--widom K]
  *         [--sk HMAX] [--profile AXIS[:NBINS]] [--profile-ik AXIS[:NBINS]]
- *         [--gcmc Z [--gc-moves K] [--gc-every M]] [--clusters RB[:MINNB]]
+ *         [--gcmc Z [--gc-moves K] [--gc-every M]] [--clusters RB[:MINNB]] [--cna RB[:MASK]]
  *         [--boo L:RB[:THRESH[:MINCONN]]] [--boo-avg RB[:NQ]] [--npt P[:DW[:EVERY]] [--w-min W] [--w-max W]]
  *         [--rdf RMAX[:NBINS]]
  *
@@ -50,6 +50,13 @@
  * line with the sweep index, the number of clusters, the largest one's size, the weight-average size
  * sum s^2 / sum s and the core ("liquid-like") fraction, then the integers behind them; at the end the
  * final state's size table, one `cluster_size` line per occupied bin of 64 (the last: sizes >= 64).
+ *
+ * --cna RB[:MASK] runs the common-neighbour analysis (pmc_common_neighbours: bond length RB <= w; MASK
+ * selects the structure types whose particles are clustered, bit 0 other, 1 fcc, 2 hcp, 3 bcc, 4
+ * icosahedral, default 30 = every crystalline type) with every report: one `cna` line with the sweep
+ * index, the number of particles of each type and the largest cluster of the selected types, then the
+ * integers behind them; at the end the final state's ten most frequent bond signatures, one `cna_sig`
+ * line each: ncn, nb, lc, ordered bonds, share.
  *
  * --boo L:RB[:THRESH[:MINCONN]] runs the bond-orientational order analysis (pmc_bond_order: l = 4 or 6,
  * bond length RB <= w, a bond is connected above THRESH, default 0.7, applied as round(256 THRESH) / 256,
@@ -154,6 +161,38 @@ static void print_clusters(pmc_ctx* ctx, unsigned step, float r_bond, int min_nb
         if (h_size[b]) printf("cluster_size %d %llu\n", b + 1, (unsigned long long)h_size[b]);
 }
 
+/* --cna: the report line of the current state (table 0) or its ten most frequent signatures (table 1) */
+static void print_cna(pmc_ctx* ctx, unsigned step, float r_bond, unsigned mask, int table) {
+    enum { NB = 64, NSIG = 2048, TOP = 10 };
+    static uint64_t h_sig[NSIG];
+    uint64_t h_size[NB];
+    pmc_cna_obs co;
+    int rc;
+    if ((rc = pmc_common_neighbours(ctx, r_bond, mask, NB, h_sig, h_size, NULL, NULL, &co)))
+        die("pmc_common_neighbours", rc);
+    if (!table) {
+        printf("cna %u other %lld fcc %lld hcp %lld bcc %lld ico %lld largest %lld (N %lld, bonds %lld, over %lld, "
+               "marked %lld, marked bonds %lld, clusters %lld, largest label %lld, sum s^2 %lld)\n", step,
+               (long long)co.types[0], (long long)co.types[1], (long long)co.types[2], (long long)co.types[3],
+               (long long)co.types[4], (long long)co.largest, (long long)co.particles, (long long)co.bonds,
+               (long long)co.over, (long long)co.marked, (long long)co.marked_bonds, (long long)co.clusters,
+               (long long)co.largest_label, (long long)co.sum_s2);
+        return;
+    }
+    uint64_t total = 0;
+    for (int b = 0; b < NSIG; ++b) total += h_sig[b];
+    printf("# bond signatures (r_bond %.9g): ncn, nb, lc (7, 15, 15: that or more), ordered bonds, share\n", (double)r_bond);
+    for (int k = 0; k < TOP; ++k) {
+        int best = -1;
+        for (int b = 0; b < NSIG; ++b)
+            if (h_sig[b] && (best < 0 || h_sig[b] > h_sig[best])) best = b;   /* ties: the smaller index */
+        if (best < 0) break;
+        printf("cna_sig %d %d %d %llu %.9g\n", best >> 8, (best >> 4) & 15, best & 15, (unsigned long long)h_sig[best],
+               (double)h_sig[best] / (double)total);
+        h_sig[best] = 0;
+    }
+}
+
 /* --boo: the report line of the current state (table 0) or its q_l table (table 1) */
 static void print_boo(pmc_ctx* ctx, unsigned step, int l, float r_bond, int c8, int min_conn, int table) {
     enum { NB = 64, NQ = 100 };
@@ -250,7 +289,8 @@ int main(int argc, char** argv) {
     long long atoms = 64;
     int passes = 1000, every = 1, graph = 0, pairobs = 0, widom = 0, sk = 0, gc_moves = 1, gc_every = 1;
     int prof_axis = -1, prof_bins = 0, ik_axis = -1, ik_bins = 0;
-    float gcmc = 0.0f, cl_rb = 0.0f;
+    float gcmc = 0.0f, cl_rb = 0.0f, cna_rb = 0.0f;
+    unsigned cna_mask = 30u;
     int npt = 0, npt_every = 1;
     float npt_p = 0.0f, npt_dw = 0.0f, w_min = 0.0f, w_max = 0.0f;
     int cl_minnb = 0, boo_l = 0, boo_c8 = 179, boo_minconn = 7;
@@ -306,6 +346,17 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "--clusters RB[:MINNB]: RB > 0, MINNB 0..127\n");
                 return 2;
             }
+            ++i;
+        }
+        else if (!strcmp(a, "--cna")) {
+            const char* colon = strchr(v, ':');
+            const long m = colon ? strtol(colon + 1, NULL, 0) : 30;
+            cna_rb = (float)atof(v);
+            if (!(cna_rb > 0.0f) || m < 0 || m > 31) {
+                fprintf(stderr, "--cna RB[:MASK]: RB > 0, MASK 0..31\n");
+                return 2;
+            }
+            cna_mask = (unsigned)m;
             ++i;
         }
         else if (!strcmp(a, "--boo-avg")) {
@@ -396,6 +447,7 @@ int main(int argc, char** argv) {
     if (rc) die("pmc_energy", rc);
     printf("0: %f\n", e);
     if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)first, cl_rb, cl_minnb, 0);
+    if (cna_rb > 0.0f) print_cna(ctx, (unsigned)first, cna_rb, cna_mask, 0);
     if (boo_l) print_boo(ctx, (unsigned)first, boo_l, boo_rb, boo_c8, boo_minconn, 0);
     if (booa_rb > 0.0f) print_boo_avg(ctx, (unsigned)first, booa_rb, booa_nq, 0);
     pmc_stats total;
@@ -457,6 +509,7 @@ int main(int argc, char** argv) {
         }
         if (gcmc == 0.0f && !npt) printf("%u: %f\n", (unsigned)(s + (uint32_t)k), e);
         if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)(s + (uint32_t)k), cl_rb, cl_minnb, 0);
+        if (cna_rb > 0.0f) print_cna(ctx, (unsigned)(s + (uint32_t)k), cna_rb, cna_mask, 0);
         if (boo_l) print_boo(ctx, (unsigned)(s + (uint32_t)k), boo_l, boo_rb, boo_c8, boo_minconn, 0);
         if (booa_rb > 0.0f) print_boo_avg(ctx, (unsigned)(s + (uint32_t)k), booa_rb, booa_nq, 0);
         if (rdf_rmax > 0.0f) print_rdf(ctx, (unsigned)(s + (uint32_t)k), rdf_rmax, rdf_bins, 0);
@@ -469,6 +522,7 @@ int main(int argc, char** argv) {
     if (seconds > 0)
         printf("# device time %.6f s, %.3e trial-moves/s\n", seconds, (double)total.trials / seconds);
     if (cl_rb > 0.0f) print_clusters(ctx, (unsigned)(first + (uint32_t)passes), cl_rb, cl_minnb, 1);
+    if (cna_rb > 0.0f) print_cna(ctx, (unsigned)(first + (uint32_t)passes), cna_rb, cna_mask, 1);
     if (boo_l) print_boo(ctx, (unsigned)(first + (uint32_t)passes), boo_l, boo_rb, boo_c8, boo_minconn, 1);
     if (booa_rb > 0.0f) print_boo_avg(ctx, (unsigned)(first + (uint32_t)passes), booa_rb, booa_nq, 1);
     if (rdf_rmax > 0.0f) print_rdf(ctx, (unsigned)(first + (uint32_t)passes), rdf_rmax, rdf_bins, 1);

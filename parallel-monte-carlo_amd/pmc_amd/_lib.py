@@ -89,6 +89,13 @@ class BooAvgObs(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("particles", "bonds", "isolated", "na_sum4", "na_sum6")]
 
 
+class CnaObs(C.Structure):
+    """``pmc_cna_obs``."""
+
+    _fields_ = ([(k, C.c_int64) for k in ("particles", "bonds", "over")] + [("types", C.c_int64 * 5)] +
+                [(k, C.c_int64) for k in ("marked", "marked_bonds", "clusters", "largest", "largest_label", "sum_s2")])
+
+
 class GcStats(C.Structure):
     """``pmc_gc_stats``."""
 
@@ -151,6 +158,8 @@ PMC_SK_MAX_K, PMC_SK_MAX_H = 4096, 1024     # include/pmc_sk.h
 PMC_PROFILE_MAX_BINS, PMC_PROFILE_BINS_PER_CELL = 4096, 64     # include/pmc_profile.h
 PMC_CLUSTER_DEG_BINS, PMC_CLUSTER_MAX_BINS = 128, 4096     # include/pmc_cluster.h
 PMC_BOO_CONN_BINS, PMC_BOO_RECORD, PMC_BOO_TERMS = 128, 16, 13     # include/pmc_boo.h
+PMC_CNA_SIG, PMC_CNA_RECORD, PMC_CNA_TYPES, PMC_CNA_MAX_NB = 2048, 8, 5, 64     # include/pmc_cna.h
+PMC_CNA_OTHER, PMC_CNA_FCC, PMC_CNA_HCP, PMC_CNA_BCC, PMC_CNA_ICO = 0, 1, 2, 3, 4
 PMC_BOO_AVG_SLOT, PMC_BOO_AVG_UNIT, PMC_BOO_K4, PMC_BOO_K6 = 4, 16, 13866, 16664     # include/pmc_boo_avg.h, pmc_boo.h
 
 
@@ -258,6 +267,7 @@ def lib():
         _sig(L, "pmc_bond_order", i32, _vp, i32, C.c_float, i32, i32, i32, i32, _vp, _vp, _vp, _vp, _vp,
              C.POINTER(BooObs))
         _sig(L, "pmc_bond_order_avg", i32, _vp, C.c_float, i32, i32, _vp, _vp, _vp, _vp, C.POINTER(BooAvgObs))
+        _sig(L, "pmc_common_neighbours", i32, _vp, C.c_float, u32, i32, _vp, _vp, _vp, _vp, C.POINTER(CnaObs))
         _sig(L, "pmc_exchange_phase", i32, _vp, i32, u32, C.c_float, i32)
         _sig(L, "pmc_exchange_sweep", i32, _vp, u32, C.c_float, i32)
         _sig(L, "pmc_gc_stats_read", i32, _vp, C.POINTER(GcStats), i32)

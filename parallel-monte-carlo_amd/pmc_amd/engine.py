@@ -21,8 +21,8 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (PMC_BOO_AVG_SLOT, PMC_BOO_CONN_BINS, PMC_BOO_RECORD, PMC_CLUSTER_DEG_BINS, PMC_IPC_HANDLE_BYTES,
-                   PMC_PROBE_INSERT, PMC_PROBE_REAL, BooAvgObs, BooObs, ClusterObs, GcStats, NptMove, NptStats, NptSums,
+from ._lib import (PMC_BOO_AVG_SLOT, PMC_BOO_CONN_BINS, PMC_BOO_RECORD, PMC_CLUSTER_DEG_BINS, PMC_CNA_RECORD, PMC_CNA_SIG,
+                   PMC_IPC_HANDLE_BYTES, PMC_PROBE_INSERT, PMC_PROBE_REAL, BooAvgObs, BooObs, ClusterObs, CnaObs, GcStats, NptMove, NptStats, NptSums,
                    PairObs, Params, ProbeObs, ProfileObs, RdfObs, Result, SkObs, Stats, check, lib)
 
 FIX_SCALE = 2.0 ** 32
@@ -619,6 +619,41 @@ class PmcContext:
         res = {key: int(getattr(out, key)) for key, _ in BooAvgObs._fields_}
         res.update(qa4_hist=qa4, qa6_hist=qa6, joint_hist=joint, slots=per, r_bond=float(np.float32(r_bond)), nq=int(nq),
                    n2=int(n2))
+        return res
+
+    def common_neighbours(self, r_bond: float = 1.5, type_mask: int = 0, nbins: int = 64, records: bool = False,
+                          labels: bool = False) -> dict:
+        """Common-neighbour analysis of a whole-box context (pmc_common_neighbours, include/pmc_cna.h):
+        the Honeycutt-Andersen signature (ncn, nb, lc) of every ordered bond (partners within r_bond <=
+        w): the common neighbours of the two ends, the bonds among them and the bonds of their largest
+        connected group; the type of every particle by the fixed-cutoff rules (0 other, 1 fcc, 2 hcp,
+        3 bcc, 4 icosahedral) and the clusters of the particles whose type is in type_mask (bit t
+        selects type t; 0b11110: every crystalline type; 0: no clusters).  Returns sig (uint64, (8, 16,
+        16): [min(ncn, 7), min(nb, 15), min(lc, 15)] counts the ordered bonds), types (int64, 5: the
+        particles per type), size_hist (uint64, nbins, as clusters()), the integers particles, bonds,
+        over (particles with more than 64 bonds: type 0, no signatures), marked, marked_bonds, clusters,
+        largest, largest_label and sum_s2, core (= marked, so that observables.cluster_size_distribution,
+        largest_cluster and mean_cluster_size work on the result), and r_bond, type_mask, nbins as used.
+        records=True adds "records": int32 (slots, 8) in slot order: type, deg, n421, n422, n444, n666,
+        n555, 0 (type -1 in an empty slot); labels=True adds "labels" as clusters() does, -1 for a
+        particle whose type is not in the mask.  Every output is exact and independent of the launch
+        shape.  observables.structure_fractions, signature_table and crystalline_fraction convert;
+        observables.add_cna accumulates samples.  Slab contexts are refused."""
+        slots = self.cells * self.nmax
+        sig = np.zeros((8, 16, 16), np.uint64)
+        size_hist = np.zeros(max(int(nbins), 0), np.uint64)
+        rec = np.empty((slots, PMC_CNA_RECORD), np.int32) if records else None
+        lab = np.empty(slots, np.int32) if labels else None
+        out = CnaObs()
+        assert sig.size == PMC_CNA_SIG
+        check("pmc_common_neighbours",
+              lib().pmc_common_neighbours(self._h, r_bond, int(type_mask), int(nbins), sig.ctypes.data,
+                                          size_hist.ctypes.data if size_hist.size else None,
+                                          rec.ctypes.data if records else None, lab.ctypes.data if labels else None,
+                                          C.byref(out)))
+        res = {key: int(getattr(out, key)) for key, _ in CnaObs._fields_ if key != "types"}
+        res.update(types=np.array(list(out.types), np.int64), sig=sig, size_hist=size_hist, records=rec, labels=lab,
+                   r_bond=float(np.float32(r_bond)), type_mask=int(type_mask), nbins=int(nbins), core=int(out.marked))
         return res
 
     def stats(self, reset: bool = False) -> dict:

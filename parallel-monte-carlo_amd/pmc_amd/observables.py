@@ -547,6 +547,56 @@ def add_bond_order_averaged(a: dict, b: dict) -> dict:
     return out
 
 
+# ---- common-neighbour analysis (PmcContext.common_neighbours) -----------------------------------------
+CNA_TYPES = ("other", "fcc", "hcp", "bcc", "ico")
+_CNA_SUMS = ("particles", "bonds", "over", "marked", "core", "marked_bonds", "clusters", "sum_s2")
+
+
+def add_cna(a: dict, b: dict) -> dict:
+    """Accumulate two common-neighbour results (samples of one run): the signature table, the type
+    counts, the size histogram and the counts add, largest keeps the maximum over the samples (with that
+    sample's largest_label), "samples" counts them and "largest_sum" adds the samples' largest sizes.
+    Records and labels are per sample and are dropped.  Refuses results taken with a different r_bond,
+    type_mask or nbins."""
+    for k in ("r_bond", "type_mask", "nbins"):
+        if a[k] != b[k]:
+            raise ValueError(f"add_cna: results taken with different {k}")
+    out = dict(a)
+    out["sig"] = np.asarray(a["sig"], np.uint64) + np.asarray(b["sig"], np.uint64)
+    out["size_hist"] = np.asarray(a["size_hist"], np.uint64) + np.asarray(b["size_hist"], np.uint64)
+    out["types"] = np.asarray(a["types"], np.int64) + np.asarray(b["types"], np.int64)
+    for k in _CNA_SUMS:
+        out[k] = int(a[k]) + int(b[k])
+    out["samples"] = int(a.get("samples", 1)) + int(b.get("samples", 1))
+    out["largest_sum"] = int(a.get("largest_sum", a["largest"])) + int(b.get("largest_sum", b["largest"]))
+    top = a if int(a["largest"]) >= int(b["largest"]) else b
+    out["largest"], out["largest_label"] = int(top["largest"]), int(top["largest_label"])
+    out["records"] = out["labels"] = None
+    return out
+
+
+def structure_fractions(res: dict) -> dict:
+    """{"other", "fcc", "hcp", "bcc", "ico"} -> the share of the particles with that type."""
+    n = float(res["particles"])
+    return {name: (float(c) / n if n > 0 else 0.0) for name, c in zip(CNA_TYPES, np.asarray(res["types"]).tolist())}
+
+
+def crystalline_fraction(res: dict) -> float:
+    """The share of the particles that are fcc, hcp or bcc."""
+    n = float(res["particles"])
+    return float(np.asarray(res["types"])[1:4].sum()) / n if n > 0 else 0.0
+
+
+def signature_table(res: dict) -> list:
+    """[((ncn, nb, lc), ordered bonds, share of the counted bonds)] of the signatures that occur, the most
+    frequent first (ties in index order).  ncn = 7, nb = 15 and lc = 15 stand for "that or more"."""
+    sig = np.asarray(res["sig"])
+    total = float(sig.sum())
+    rows = [(tuple(int(v) for v in k), int(sig[tuple(k)])) for k in np.argwhere(sig)]
+    rows.sort(key=lambda kv: (-kv[1], kv[0]))
+    return [(k, c, c / total) for k, c in rows]
+
+
 # ---- g(r) beyond the cutoff (PmcContext.rdf_long, include/pmc_rdf.h) ----------------------------
 
 def add_rdf(a: dict, b: dict) -> dict:
